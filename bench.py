@@ -5,8 +5,13 @@ HBM. Default (--config 4): the north-star shape, i.e. one GPU's shard of BASELIN
 B=256 objects/GPU, N=1024 points, K=50 candidates, T=500 PC steps, ScoreNet encoder + sampler,
 EnergyNet encoder + energy, ranking + aggregation (runners/evaluation_single.py:78-219 per batch).
 --config 2 is ScoreNet only at B=64, --config 3 adds EnergyNet at B=64, --config 5 is the B=256,
-N=2048, K=100, T=1000 + ScaleNet stress case. PC runs also time the shipped ODE sampler
-(T0=0.55) on the same objects and report it under "ode".
+N=2048, K=100, T=1000 + ScaleNet stress case.
+
+A plain run sets up, warms up, times --steps steps and prints one JSON result line; --dump-outputs DIR
+also writes the last timed step's outputs as DIR/<name>.npy. --full adds everything beside the headline
+figure: the sampler roofline of the timed steps, the same steps in exact fp32 ("f32_exact"), the shipped
+ODE sampler (T0=0.55) on the same objects ("ode"), the DINO-pointwise pipeline ("pointwise") and the
+oracle CPU baseline ("cpu_baseline").
 
 Multi-GPU: one process per GPU (torchrun), objects sharded (weak scaling: B objects per GPU),
 packed weights broadcast once from rank 0 over RCCL, no collective on the timed data path.
@@ -396,6 +401,15 @@ def time_ode_calls(args, cfg, data0, B, K, ws, dev):
     return out
 
 
+def dump_outputs(path, outs):
+    """--dump-outputs: every array the last timed step handed to its caller as <name>.npy under `path`, float64
+    where the path computes in float64 and float32 otherwise (config 5, the largest: 256 x 100 x (9 + 7) values)."""
+    os.makedirs(path, exist_ok=True)
+    for name, t in outs.items():
+        t = t.detach().cpu()
+        np.save(os.path.join(path, f"{name}.npy"), (t if t.dtype == torch.float64 else t.to(torch.float32)).numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -440,8 +454,20 @@ def main():
                     help="Light-encoder PC runs of a full-pipeline config: also time this many steps of the shipped "
                          "scripts' encoder (scripts/eval_single.sh: --dino pointwise) on the same shape and report them "
                          "under 'pointwise' (0: off)")
+    ap.add_argument("--full", action="store_true",
+                    help="also report everything beside the headline figure: the sampler roofline of the timed steps "
+                         "(their sampler launches bracketed by HIP events), the 'f32_exact', 'ode' and 'pointwise' legs "
+                         "and the oracle CPU baseline, each still governed by its own option above. Off by default: a "
+                         "plain run sets up, warms up, times --steps steps and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to its caller (pose candidates "
+                         "and, as the config has them, energies, the aggregated pose, ScaleNet's lengths) as "
+                         "DIR/<name>.npy. Inputs, weights and noise are seeded: the same arguments give the same inputs")
     ap.add_argument("--launch-probe", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if not args.full:   # a plain run: the headline figure only
+        args.ode_calls = args.f32_steps = args.pointwise_steps = 0
+        args.no_cpu_baseline = True
     ndev = 0
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and not args.launch_probe:
         ndev = count_gpus()
@@ -560,10 +586,11 @@ def main():
             if score.after_encode is not None:
                 score.after_encode()
             hook, score.after_encode = score.after_encode, None
-            pose, _ = score.pred_func(data, repeat_num=K, extract_feature=False)
+            pose, q = score.pred_func(data, repeat_num=K, extract_feature=False)
             score.after_encode = hook
         else:
-            pose, _ = score.pred_func(data, repeat_num=K, T0=args.t0 if ode else None)
+            pose, q = score.pred_func(data, repeat_num=K, T0=args.t0 if ode else None)
+        outs = {"pred_pose": pose, "pred_q": q}   # what the step hands to its caller (--dump-outputs)
         if ode:
             nfevs.append(score.last_nfev)
         if record and not ode:
@@ -578,12 +605,14 @@ def main():
                 edata["_energy_pobj"][1].record_stream(stream)
             e = energy.get_energy(edata, pose, T=1e-5, extract_feature=False)
             agg = aggregate.aggregate_pose(pose, e)
+            outs.update(energy=e, aggregated_pose=agg)
             if scale is not None:
-                scale.pred_scale_func({"pts_feat": data["pts_feat"], "axes": agg[:, :3, :3].contiguous()})
+                _, outs["length"] = scale.pred_scale_func({"pts_feat": data["pts_feat"],
+                                                           "axes": agg[:, :3, :3].contiguous()})
         elif scale is not None:
             axes = torch.eye(3, device=dev).expand(B, 3, 3).contiguous()
-            scale.pred_scale_func({"pts_feat": data["pts_feat"], "axes": axes})
-        return pose
+            _, outs["length"] = scale.pred_scale_func({"pts_feat": data["pts_feat"], "axes": axes})
+        return outs
 
     def timed_steps(n, leg=None, evs=None):
         """n steps between a barrier + device synchronisation on both sides; the max over ranks (s)."""
@@ -611,8 +640,11 @@ def main():
         dist.barrier()
     torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
+    last_outs = None
     for i in range(args.steps):
-        one_step(record=True, last=i == args.steps - 1)
+        outs = one_step(record=args.full, last=i == args.steps - 1)
+        last_outs = outs if i == args.steps - 1 else None
+        del outs
     torch.cuda.synchronize(dev)
     if ws > 1:
         dist.barrier()
@@ -623,6 +655,9 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
+    if args.dump_outputs and rank == 0 and last_outs is not None:
+        dump_outputs(args.dump_outputs, last_outs)
+    last_outs = None
     if ode:
         report_ode(args, B, N, K, ws, rank, elapsed, nfevs[-args.steps:], cfgd)
         if ws > 1:
@@ -700,18 +735,35 @@ def main():
         del pw
         torch.cuda.empty_cache()
     units = B * K * T * ws * args.steps
-    samp_ms = float(np.mean([a.elapsed_time(b) for a, b in samp_ev]))
-    per_launch_s = samp_ms / 1e3 / (T + 1)
-    flop_launch = B * K * arch.score_flops_per_candidate_step()
-    achieved = flop_launch / per_launch_s / 1e12
-    # f16x3: the two per-candidate GEMMs run 6 f16 MFMA products per fp32 MAC (three planes per operand),
-    # so their MFMA ceiling in algorithmic (fp32) FLOP/s is the dense f16 peak / 6
-    peak = F16_PEAK_TFLOPS / 6 if fast else FP32_PEAK_TFLOPS
-    up = score.heads.up.t
-    wg_bytes = sum(up[k].numel() * up[k].element_size() for k in
-                   (("pe2_h", "h1p_h") if fast else ("pe2_w", "h1p_w")))   # streamed per workgroup per step
-    tile = int(_tile_rows(B * K, fast))   # the kernel's real tile width
-    nwg = -(-B * K // tile)
+    roofline = None
+    if args.full:   # the PC sampler launches of the timed steps, bracketed by HIP events
+        samp_ms = float(np.mean([a.elapsed_time(b) for a, b in samp_ev]))
+        per_launch_s = samp_ms / 1e3 / (T + 1)
+        flop_launch = B * K * arch.score_flops_per_candidate_step()
+        achieved = flop_launch / per_launch_s / 1e12
+        # f16x3: the two per-candidate GEMMs run 6 f16 MFMA products per fp32 MAC (three planes per operand),
+        # so their MFMA ceiling in algorithmic (fp32) FLOP/s is the dense f16 peak / 6
+        peak = F16_PEAK_TFLOPS / 6 if fast else FP32_PEAK_TFLOPS
+        up = score.heads.up.t
+        wg_bytes = sum(up[k].numel() * up[k].element_size() for k in
+                       (("pe2_h", "h1p_h") if fast else ("pe2_w", "h1p_w")))   # streamed per workgroup per step
+        tile = int(_tile_rows(B * K, fast))   # the kernel's real tile width
+        nwg = -(-B * K // tile)
+        roofline = {"bound": "mfma", "achieved": achieved, "peak": peak, "unit": "TFLOP/s",
+                    "frac": achieved / peak, "traffic": load_traffic(B * K, fast, tile),
+                    "kernel": "pc_step_kernel", "arith": score.heads.arith, "flop_per_launch": flop_launch,
+                    "avg_launch_us": per_launch_s * 1e6, "sampler_ms_per_step": samp_ms,
+                    "fp32_mfma_equiv_frac": achieved / FP32_PEAK_TFLOPS,
+                    # every workgroup streams the GEMM weights from L2
+                    "l2_weight_stream": {"bytes_per_workgroup": wg_bytes, "workgroups": nwg,
+                                         "candidates_per_workgroup": tile,
+                                         "GBps_per_CU": wg_bytes / per_launch_s / 1e9,
+                                         "TBps_chip": wg_bytes * nwg / per_launch_s / 1e12}}
+        rp = load_rocprof(f"void pc_step_kernel<{tile // 16}, 8, {3 if fast else 0}>", args.config, args.dino)
+        if rp is not None:   # the committed rocprofv3 --stats of a bench run: its mean launch, same FLOPs
+            rp["achieved"] = flop_launch / (rp["avg_launch_us"] * 1e-6) / 1e12
+            rp["frac"] = rp["achieved"] / peak
+            roofline["rocprof"] = rp
     if rank == 0:
         out = {
             "metric": "pose candidates/sec (B objs x K cands x T denoise steps)",
@@ -737,22 +789,9 @@ def main():
                        "shared_geometry": bool(args.share_geometry and cfgd["energy"] and not args.pipeline),
                        "energy_encoder": (["after the sampler", "beside the sampler", "beside the score encoder"]
                                           [args.energy_overlap] if cfgd["energy"] else None)},
-            "roofline": {"bound": "mfma", "achieved": achieved, "peak": peak, "unit": "TFLOP/s",
-                         "frac": achieved / peak, "traffic": load_traffic(B * K, fast, tile),
-                         "kernel": "pc_step_kernel", "arith": score.heads.arith, "flop_per_launch": flop_launch,
-                         "avg_launch_us": per_launch_s * 1e6, "sampler_ms_per_step": samp_ms,
-                         "fp32_mfma_equiv_frac": achieved / FP32_PEAK_TFLOPS,
-                         # every workgroup streams the GEMM weights from L2
-                         "l2_weight_stream": {"bytes_per_workgroup": wg_bytes, "workgroups": nwg,
-                                              "candidates_per_workgroup": tile,
-                                              "GBps_per_CU": wg_bytes / per_launch_s / 1e9,
-                                              "TBps_chip": wg_bytes * nwg / per_launch_s / 1e12}},
         }
-        rp = load_rocprof(f"void pc_step_kernel<{tile // 16}, 8, {3 if fast else 0}>", args.config, args.dino)
-        if rp is not None:   # the committed rocprofv3 --stats of a bench run: its mean launch, same FLOPs
-            rp["achieved"] = flop_launch / (rp["avg_launch_us"] * 1e-6) / 1e12
-            rp["frac"] = rp["achieved"] / peak
-            out["roofline"]["rocprof"] = rp
+        if roofline is not None:
+            out["roofline"] = roofline
         if f32_info is not None:
             out["f32_exact"] = f32_info
         if ode_info is not None:

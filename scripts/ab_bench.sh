@@ -4,6 +4,7 @@
 # usage: bash scripts/ab_bench.sh TAG ROUNDS "BENCH ARGS" LIB1 LIB2 ...
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
 TAG=$1; ROUNDS=$2; ARGS=$3; shift 3
+ARGS="--full $ARGS"   # the roofline read below is part of the full report
 for r in $(seq 1 "$ROUNDS"); do
   for L in "$@"; do
     GENPOSE_HIP_LIB=$L timeout -k 10 300 python bench.py $ARGS > gpurun_out/${TAG}.json 2> gpurun_out/${TAG}.err || exit 1

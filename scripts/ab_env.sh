@@ -3,6 +3,7 @@
 # usage: bash scripts/ab_env.sh TAG ROUNDS "BENCH ARGS" VAR VALUE1 VALUE2 ...
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
 TAG=$1; ROUNDS=$2; ARGS=$3; VAR=$4; shift 4
+ARGS="--full $ARGS"   # the roofline read below is part of the full report
 for r in $(seq 1 "$ROUNDS"); do
   for V in "$@"; do
     env "$VAR=$V" timeout -k 10 300 python bench.py $ARGS > gpurun_out/${TAG}.json 2> gpurun_out/${TAG}.err || exit 1

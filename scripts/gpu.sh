@@ -6,7 +6,7 @@
 #   tests:EXPR       the same with -k EXPR (commas for spaces: tests:a,or,b)
 #   smoke            __graft_entry__.smoke()
 #   bench[:ARGS]     python bench.py ARGS (comma-separated, e.g. bench:--config,5,--steps,2)
-#   prof[:ARGS]      rocprofv3 --kernel-trace --stats of bench.py ARGS (--steps 3 --warmup 1 by default)
+#   prof[:ARGS]      rocprofv3 --kernel-trace --stats of bench.py ARGS (--full --steps 3 --warmup 1 by default)
 #   bin:PROGRAM[:ARGS] a built program (e.g. scripts/mfma_round_probe)
 #   env:NAME=VALUE   export NAME=VALUE for the steps after it (env:NAME= unsets it)
 #   ab:MODE,ROUNDS,LIB1,LIB2,...  scripts/ab.sh (same-box A/B of library variants)
@@ -32,7 +32,7 @@ for step in "$@"; do
     bench)
       timeout -k 10 600 python bench.py "${A[@]}" > $out.json 2> $out.err ;;
     prof)
-      [ ${#A[@]} -eq 0 ] && A=(--steps 3 --warmup 1 --no-cpu-baseline)
+      [ ${#A[@]} -eq 0 ] && A=(--full --steps 3 --warmup 1 --no-cpu-baseline)
       rm -rf $out
       timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out -o k -- python3 bench.py "${A[@]}" > $out.log 2>&1 ;;
     bin)

@@ -579,6 +579,17 @@ def test_bench_gpus2_without_gpus_fails_loudly():
     assert '"n_gpus"' not in p.stdout
 
 
+def test_bench_has_full_and_dump_options(monkeypatch, capsys):
+    """bench.py takes --full (everything beside the headline figure) and --dump-outputs DIR."""
+    b = _bench_module()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--help"])
+    with pytest.raises(SystemExit) as e:
+        b.main()
+    assert e.value.code == 0
+    text = capsys.readouterr().out
+    assert "--full" in text and "--dump-outputs DIR" in text
+
+
 def test_bench_counts_gpus_without_hip(monkeypatch, tmp_path):
     """bench.py --gpus N counts the node's GPUs before the launcher starts, without any HIP call: amdsmi,
     else the KFD topology (nodes with a non-zero gfx_target_version); with neither it exits non-zero and
