@@ -101,6 +101,15 @@ _SIGS: Dict[str, tuple] = {
     "gp_ode_attempt": (c_int, [ctypes.POINTER(HeadWeights), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_double, c_double, c_int, c_int,
                                c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "gp_score_div_eval": (c_int, [ctypes.POINTER(HeadWeights), c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_int,
+                                  c_int, c_void_p, c_void_p, c_void_p]),
+    "gp_like_workspace_size": (c_size_t, [c_int]),
+    "gp_like_rhs": (c_int, [ctypes.POINTER(HeadWeights), c_void_p, c_float, c_float, c_double, c_void_p, c_void_p,
+                            c_void_p, c_void_p, c_int, c_double, c_int, c_int, c_void_p, c_void_p, c_size_t,
+                            c_void_p]),
+    "gp_like_attempt": (c_int, [ctypes.POINTER(HeadWeights), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_double, c_double,
+                                c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "gp_ode_init_norms": (c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_longlong, c_double, c_double, c_void_p,
                                   c_void_p]),
     "gp_ode_dense": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_double, c_double,

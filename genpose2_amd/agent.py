@@ -17,7 +17,7 @@ import torch
 
 from . import aggregate, arch, device as dev, sde, weights
 from .config import GenPoseConfig
-from .ode import DeviceRk45, GlobalDeviceRk45, rk45_device, rk45_drive, time_scalars
+from .ode import DeviceRk45, GlobalDeviceRk45, LikelihoodRk45, rk45_device, rk45_drive, time_scalars
 
 
 def _as_config(cfg) -> GenPoseConfig:
@@ -382,6 +382,54 @@ class PoseNet:
                 energy[rows] = self.heads.energy(pobj[objs].contiguous(), trow, sig, pose[rows].contiguous(), K)
         self._calls += 1
         return energy.view(bs, K, -1)
+
+    # ------------------------------------------------------------------ get_likelihood
+    @torch.no_grad()
+    def get_likelihood(self, data, pose_samples, extract_feature=True, epsilon=None, atol=1e-5, rtol=1e-5,
+                       return_latent=False):
+        """GFObjectPose.forward(data, mode="likelihood") (posenet.py:278-292, cond_ode_likelihood,
+        samplers.py:25-110): each pose's log-likelihood in bits under the ScoreNet, by the probability-flow ODE
+        from eps to 1 over [x | logp] with a Skilling-Hutchinson divergence estimate (forward mode on device,
+        ode.LikelihoodRk45; scipy's RK45 controller on host scalars).
+
+        pose_samples (bs,K,9): poses in the camera frame as pred_func returns them (pts_center is subtracted, as
+        get_energy does). epsilon: the (bs*K,9) Hutchinson direction used as is; None draws the reference's
+        prior((R,9)) = randn * sigma(T=1) (noise_feed.prior if set, else the agent's generator).
+        Returns (bs,K) float64, plus the latent z (bs,K,9) float64 with return_latent. Sets last_nfev."""
+        if self.cfg.agent_type != "score":
+            raise NotImplementedError("get_likelihood needs agent_type='score'")
+        if self.global_batch is not None:
+            raise NotImplementedError("get_likelihood has no global-batch mode")
+        self.is_testing = True
+        bs, K = pose_samples.shape[0], pose_samples.shape[1]
+        R = bs * K
+        feat = self._encode(data) if extract_feature else dev.require_device_tensor(data["pts_feat"], "pts_feat")
+        data["pts_feat"] = feat
+        pobj = self.heads.object_proj(feat)
+        pose = pose_samples.to(self.device).reshape(R, -1).to(torch.float32).clone()
+        center = dev.require_device_tensor(data["pts_center"], "pts_center")
+        pose[:, -3:] -= center.unsqueeze(1).repeat(1, K, 1).view(R, -1)
+        if epsilon is None:
+            epsilon = self._draw_prior(R) * sde.prior_sigma(arch.SDE_T)
+        eps_dir = epsilon.to(self.device, torch.float32).reshape(R, arch.POSE_DIM).contiguous()
+        be = LikelihoodRk45(self.heads, pobj, pose, eps_dir, K, rtol=rtol, atol=atol)
+        # solve_ivp(ode_func, (eps, 1.0), init_inp) without t_eval; a failed solve (status -1) still hands
+        # res.y[:, -1] on (samplers.py:97-100): rk45_drive warns and keeps the last state
+        _, nfev, _ = rk45_drive(be, arch.SAMPLING_EPS, 1.0, rtol=rtol, atol=atol, keep_all=False)
+        self.last_nfev = nfev
+        self._calls += 1
+        zp = be.ys[-1]
+        z = zp[: R * arch.POSE_DIM].view(R, arch.POSE_DIM)
+        delta_logp = zp[R * arch.POSE_DIM:]
+        # global_prior_likelihood (samplers.py:14-22) with the reference's scalar types: sigma_max is the float32
+        # sigma(1.0), the log term a float32 scalar, z float64
+        sigma_max = sde.sigma(torch.tensor(1.0))
+        log_term = float(-arch.POSE_DIM / 2.0 * torch.log(2 * np.pi * sigma_max ** 2))
+        prior_logp = log_term - torch.sum(z ** 2, dim=-1) / float(2 * sigma_max ** 2)
+        ll = ((prior_logp + delta_logp) / np.log(2)).view(bs, K)
+        if return_latent:
+            return ll, z.view(bs, K, arch.POSE_DIM).clone()
+        return ll
 
     # ------------------------------------------------------------------ pred_scale_func
     @torch.no_grad()

@@ -152,15 +152,37 @@ __device__ __forceinline__ void stream_layer(__amdgpu_buffer_rsrc_t W, const int
     stream_step<0, KG + D, TT, NT, KG, D>(W, T, B, lane, lane * 16, ring, acc);
 }
 
+// Forward-mode derivative (JVP) trunks: the upper half of the column tiles (ct >= NT / 2) carries a tangent
+// of the lower half's poses (column c + 8 NT is the tangent of column c; its xin row is the direction eps).
+// A tangent tile runs through the same GEMMs on the same weight fragments as its primal tile, without the
+// bias / pobj / tproj terms, and takes each ReLU's mask from the primal's pre-activation (torch: relu' = 0
+// at 0): it sits in the same lane and accumulator slot, so the mask needs no exchange. head_out_tan then
+// gives (d head / d pose) . eps.
+__device__ __forceinline__ f32x4 mask4(f32x4 d, f32x4 pre) {
+    return f32x4{pre.x > 0.f ? d.x : 0.f, pre.y > 0.f ? d.y : 0.f, pre.z > 0.f ? d.z : 0.f, pre.w > 0.f ? d.w : 0.f};
+}
+// Tangent head output o of tangent column c (JVP trunks): the per-wave partials in wave order, no bias.
+template <int NT, int WV, int PL>
+__device__ __forceinline__ float head_out_tan(const HeadSmem<NT, WV, PL>& sm, int c, int o) {
+    const int h = o / 3;
+    const int v = (h * NT + (c >> 4)) * 3 + (o - 3 * h);
+    float acc = 0.f;
+#pragma unroll
+    for (int w = 0; w < WV; ++w) acc += sm.red[v][c & 15][w];
+    return acc;
+}
+
 // Computes the head outputs (read with head_out) for the candidates of this workgroup. Starts with
 // the workgroup barrier that publishes sm.xin, obj_of_col and the staged weights (callers write
 // them before the call without a barrier of their own; the first weight loads are issued before it).
 // `obj_of_col` maps column -> object row of pobj; `tproj` is the 768-vector of this time value.
-template <int NT, int WV>
+template <int NT, int WV, bool JVP = false>
 __device__ __forceinline__ void head_trunk(const gp_head_weights& w, const float* __restrict__ pobj,
                            const float* __restrict__ tproj, const int* obj_of_col, HeadSmem<NT, WV>& sm,
                            int trace_slot = 0) {
     constexpr int TPW = 16 / WV;   // output tiles per wave and per 256-wide layer
+    constexpr int NP = JVP ? NT / 2 : NT;   // primal column tiles (tangent tile ct pairs with ct - NP)
+    static_assert(!JVP || NT % 2 == 0, "a JVP trunk pairs every primal tile with a tangent tile");
     static_assert(!HeadSmem<NT, WV>::kAliasAct, "the exact-fp32 trunk keeps separate activation buffers");
     const int lane = threadIdx.x & 63;
     const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // wave-uniform (SGPR)
@@ -196,9 +218,19 @@ __device__ __forceinline__ void head_trunk(const gp_head_weights& w, const float
             const int T = wid * TPW + t;
             const f32x4 a = sm.pe0w[T * 64 + lane];
             const f32x4 bias = ld4(&sm.pe0b[16 * T + 4 * q]);
+            if constexpr (JVP) {
 #pragma unroll
-            for (int ct = 0; ct < NT; ++ct)
-                sm.act1[(T * NT + ct) * 64 + lane] = relu4(mfma_kgroup(a, bf[ct], f32x4{0.f, 0.f, 0.f, 0.f}) + bias);
+                for (int ct = 0; ct < NP; ++ct) {
+                    const f32x4 pre = mfma_kgroup(a, bf[ct], f32x4{0.f, 0.f, 0.f, 0.f}) + bias;
+                    sm.act1[(T * NT + ct) * 64 + lane] = relu4(pre);
+                    sm.act1[(T * NT + NP + ct) * 64 + lane] =
+                        mask4(mfma_kgroup(a, bf[NP + ct], f32x4{0.f, 0.f, 0.f, 0.f}), pre);
+                }
+            } else {
+#pragma unroll
+                for (int ct = 0; ct < NT; ++ct)
+                    sm.act1[(T * NT + ct) * 64 + lane] = relu4(mfma_kgroup(a, bf[ct], f32x4{0.f, 0.f, 0.f, 0.f}) + bias);
+            }
         }
     }
     __syncthreads();
@@ -208,13 +240,13 @@ __device__ __forceinline__ void head_trunk(const gp_head_weights& w, const float
     // (hoisted pts/t blocks) are issued, so their latency hides behind MFMAs
     constexpr int PE2_TAIL = 4;
     stream_step<D2, KG_HID + D2 - PE2_TAIL, TPW, NT, KG_HID, D2>(W2, T2, sm.act1, lane, voff, ring2, acc2);
-    f32x4 tpv[3 * TPW], pov[3 * TPW][NT];
+    f32x4 tpv[3 * TPW], pov[3 * TPW][NP];
 #pragma unroll
     for (int i = 0; i < 3 * TPW; ++i) {
         const int T = TH[i];
         tpv[i] = ld4(tproj + 16 * T + 4 * q);
 #pragma unroll
-        for (int ct = 0; ct < NT; ++ct) pov[i][ct] = ld4(pobj + (size_t)obj_of_col[ct * 16 + n] * (3 * HID) + 16 * T + 4 * q);
+        for (int ct = 0; ct < NP; ++ct) pov[i][ct] = ld4(pobj + (size_t)obj_of_col[ct * 16 + n] * (3 * HID) + 16 * T + 4 * q);
     }
     stream_step<KG_HID + D2 - PE2_TAIL, KG_HID + D2, TPW, NT, KG_HID, D2>(W2, T2, sm.act1, lane, voff, ring2, acc2);
     // ---- head layer 1 prologue, issued before the barrier: the first DH k-groups of the pose-block
@@ -224,14 +256,27 @@ __device__ __forceinline__ void head_trunk(const gp_head_weights& w, const float
 #pragma unroll
     for (int i = 0; i < 3 * TPW; ++i)
 #pragma unroll
-        for (int ct = 0; ct < NT; ++ct) acc[i][ct] = pov[i][ct] + tpv[i];
+        for (int ct = 0; ct < NT; ++ct) {
+            if constexpr (JVP) {
+                if (ct < NP) acc[i][ct] = pov[i][ct < NP ? ct : 0] + tpv[i];
+                else acc[i][ct] = f32x4{0.f, 0.f, 0.f, 0.f};
+            } else {
+                acc[i][ct] = pov[i][ct] + tpv[i];
+            }
+        }
     f32x4 ringh[DH + 1][3 * TPW];
     stream_step<0, DH, 3 * TPW, NT, KG_HID, DH>(WH, TH, sm.act2, lane, voff, ringh, acc);
 #pragma unroll
     for (int t = 0; t < TPW; ++t) {
         const f32x4 bias = ld4(&sm.pe2b[16 * T2[t] + 4 * q]);
 #pragma unroll
-        for (int ct = 0; ct < NT; ++ct) sm.act2[(T2[t] * NT + ct) * 64 + lane] = relu4(acc2[t][ct] + bias);
+        for (int ct = 0; ct < NT; ++ct) {
+            if constexpr (JVP)
+                sm.act2[(T2[t] * NT + ct) * 64 + lane] =
+                    ct < NP ? relu4(acc2[t][ct] + bias) : mask4(acc2[t][ct], acc2[t][ct < NP ? 0 : ct - NP] + bias);
+            else
+                sm.act2[(T2[t] * NT + ct) * 64 + lane] = relu4(acc2[t][ct] + bias);
+        }
     }
     __syncthreads();
     PC_MARK(4);
@@ -246,7 +291,12 @@ __device__ __forceinline__ void head_trunk(const gp_head_weights& w, const float
             float p0 = 0.f, p1 = 0.f, p2 = 0.f;
 #pragma unroll
             for (int t = 0; t < TPW; ++t) {
-                const f32x4 u = relu4(acc[h * TPW + t][ct]);
+                f32x4 u;
+                if constexpr (JVP)
+                    u = ct < NP ? relu4(acc[h * TPW + t][ct])
+                                : mask4(acc[h * TPW + t][ct], acc[h * TPW + t][ct < NP ? 0 : ct - NP]);
+                else
+                    u = relu4(acc[h * TPW + t][ct]);
                 const int ch = 16 * (wid * TPW + t) + 4 * q;
                 const f32x4 w0 = ld4(&sm.h2w[(h * 3 + 0) * HID + ch]);
                 const f32x4 w1 = ld4(&sm.h2w[(h * 3 + 1) * HID + ch]);
@@ -630,16 +680,16 @@ __device__ __forceinline__ void stream_x3_step(__amdgpu_buffer_rsrc_t W, const i
 // wave's output tiles of head H: loads issued where their latency hides (under the previous head's epilogue,
 // or the pose_encoder.2 epilogue for head 0) and folded into the accumulator at the head's start, so they are
 // not live across the MFMA stream.
-template <int H, int NT, int TPW>
+template <int H, int NT, int TPW, int NP = NT>   // NP: column tiles with init rows (the primal tiles of a JVP trunk)
 __device__ __forceinline__ void head_x3_init_load(__amdgpu_buffer_rsrc_t RP, __amdgpu_buffer_rsrc_t RT, const int (&vo)[NT],
-                                                  int wid, int lane, f32x4 (&tpv)[TPW], f32x4 (&pov)[TPW][NT]) {
+                                                  int wid, int lane, f32x4 (&tpv)[TPW], f32x4 (&pov)[TPW][NP]) {
     const int q = lane >> 4;
 #pragma unroll
     for (int t = 0; t < TPW; ++t) {
         const int T = H * 16 + wid * TPW + t;
         tpv[t] = ldbuf4(RT, 16 * q, 64 * T);
 #pragma unroll
-        for (int ct = 0; ct < NT; ++ct) pov[t][ct] = ldbuf4(RP, vo[ct], 64 * T);
+        for (int ct = 0; ct < NP; ++ct) pov[t][ct] = ldbuf4(RP, vo[ct], 64 * T);
     }
 }
 
@@ -651,13 +701,14 @@ __device__ __forceinline__ void head_x3_init_load(__amdgpu_buffer_rsrc_t RP, __a
 // PRE: the caller wrote every column's ColScales to sm.cscl before the trunk's first barrier (the PC
 // step's update waves, which hold the rows), so the trunk reads them instead of recomputing them in
 // every wave.
-template <int H, int NT, int WV, int TPW, int DH>
+template <int H, int NT, int WV, int TPW, int DH, bool JVP = false>
 __device__ __forceinline__ void head_x3_head(__amdgpu_buffer_rsrc_t WH, const f16x8* __restrict__ act2h,
                                              __amdgpu_buffer_rsrc_t RP, __amdgpu_buffer_rsrc_t RT, const int (&vo)[NT],
                                              HeadSmem<NT, WV, X3P>& sm, const float (&uh)[NT], const float (&sh)[NT],
                                              int wid, int lane, f16x8 (&ringh)[DH + 1][TPW][X3P],
-                                             f32x4 (&tpv)[TPW], f32x4 (&pov)[TPW][NT],
+                                             f32x4 (&tpv)[TPW], f32x4 (&pov)[TPW][JVP ? NT / 2 : NT],
                                              float (&pv)[HeadSmem<NT, WV, X3P>::kRedV]) {
+    constexpr int NP = JVP ? NT / 2 : NT;
     const int q = lane >> 4, n = lane & 15;
     const int voff = lane * 16;
     int TH[TPW];
@@ -668,7 +719,12 @@ __device__ __forceinline__ void head_x3_head(__amdgpu_buffer_rsrc_t WH, const f1
     for (int t = 0; t < TPW; ++t)
 #pragma unroll
         for (int ct = 0; ct < NT; ++ct) {
-            acc[t][ct] = (pov[t][ct] + tpv[t]) * sh[ct];
+            if constexpr (JVP) {
+                if (ct < NP) acc[t][ct] = (pov[t][ct < NP ? ct : 0] + tpv[t]) * sh[ct];
+                else acc[t][ct] = f32x4{0.f, 0.f, 0.f, 0.f};
+            } else {
+                acc[t][ct] = (pov[t][ct] + tpv[t]) * sh[ct];
+            }
             cor[t][ct] = f32x4{0.f, 0.f, 0.f, 0.f};
         }
     stream_x3_step<DH, KC_HID + DH, TPW, NT, DH>(WH, TH, act2h, lane, voff, ringh, acc, cor);
@@ -677,7 +733,7 @@ __device__ __forceinline__ void head_x3_head(__amdgpu_buffer_rsrc_t WH, const f1
 #pragma unroll
         for (int t = 0; t < TPW; ++t) TN[t] = TH[t] + 16;
         stream_x3_step<0, DH, TPW, NT, DH>(WH, TN, act2h, lane, voff, ringh, acc, cor);
-        head_x3_init_load<H + 1, NT, TPW>(RP, RT, vo, wid, lane, tpv, pov);
+        head_x3_init_load<H + 1, NT, TPW, NP>(RP, RT, vo, wid, lane, tpv, pov);
     }
     // nothing below is scheduled into the MFMA stream above: interleaved there, the row swaps of the
     // reduce-scatter reused registers in-flight MFMAs still read (v_permlane*_swap writes both operands)
@@ -704,7 +760,15 @@ __device__ __forceinline__ void head_x3_head(__amdgpu_buffer_rsrc_t WH, const f1
         const f32x4 w2 = ld4(&sm.h2w[(H * 3 + 2) * HID + ch]);
 #pragma unroll
         for (int ct = 0; ct < NT; ++ct) {
-            const f32x4 u = relu4((acc[t][ct] + cor[t][ct]) * uh[ct]);
+            f32x4 u;
+            if constexpr (JVP) {
+                constexpr int NPP = JVP ? NP : 0;
+                const int cp = ct < NPP ? 0 : ct - NPP;   // a tangent tile's primal tile
+                u = ct < NPP ? relu4((acc[t][ct] + cor[t][ct]) * uh[ct])
+                             : mask4((acc[t][ct] + cor[t][ct]) * uh[ct], (acc[t][cp] + cor[t][cp]) * uh[cp]);
+            } else {
+                u = relu4((acc[t][ct] + cor[t][ct]) * uh[ct]);
+            }
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 p[ct][0] = __builtin_fmaf(u[j], w0[j], p[ct][0]);
@@ -727,7 +791,7 @@ __device__ __forceinline__ void head_x3_head(__amdgpu_buffer_rsrc_t WH, const f1
     __builtin_amdgcn_sched_barrier(0);
 }
 
-template <int NT, int WV, bool PRE = false>
+template <int NT, int WV, bool PRE = false, bool JVP = false>
 __device__ __forceinline__ void head_trunk_x3(const gp_head_weights& w, const float* __restrict__ pobj,
                                               const float* __restrict__ tproj, const int* obj_of_col,
                                               HeadSmem<NT, WV, X3P>& sm, int trace_slot, const SplitScalars hs) {
@@ -735,6 +799,8 @@ __device__ __forceinline__ void head_trunk_x3(const gp_head_weights& w, const fl
     static_assert(TPW % 2 == 0, "the f16x3 trunk pairs a wave's output tiles into 32-deep chunks");
     static_assert(TPW <= 4, "SplitScalars carries at most four pose_encoder.0 tiles per wave");
     constexpr int CPW = TPW / 2;
+    constexpr int NP = JVP ? NT / 2 : NT;   // primal column tiles (tangent tile ct pairs with ct - NP)
+    static_assert(!JVP || NT % 2 == 0, "a JVP trunk pairs every primal tile with a tangent tile");
     using SM = HeadSmem<NT, WV, X3P>;
     const int tid = tid_x();
     const int lane = tid & 63;
@@ -784,12 +850,24 @@ __device__ __forceinline__ void head_trunk_x3(const gp_head_weights& w, const fl
         const f32x4 a0 = hs.pe0a[2 * c], a1 = hs.pe0a[2 * c + 1];
         const f32x4 bias0 = hs.pe0b[2 * c], bias1 = hs.pe0b[2 * c + 1];
 #pragma unroll
-        for (int ct = 0; ct < NT; ++ct) {
+        for (int ct = 0; ct < NP; ++ct) {
             const f32x4 z = f32x4{0.f, 0.f, 0.f, 0.f};
             f16x8 pl[X3P];
-            split3_pair(relu4(mfma_kgroup(a0, bf[ct], z) + bias0), relu4(mfma_kgroup(a1, bf[ct], z) + bias1), s1[ct], pl);
+            if constexpr (JVP) {   // the tangent tile: no bias, the primal's masks; its own bound (s1 of its eps row)
+                constexpr int dt = JVP ? NP : 0;
+                const f32x4 pre0 = mfma_kgroup(a0, bf[ct], z) + bias0, pre1 = mfma_kgroup(a1, bf[ct], z) + bias1;
+                split3_pair(relu4(pre0), relu4(pre1), s1[ct], pl);
 #pragma unroll
-            for (int p = 0; p < X3P; ++p) act1h[(((Ta >> 1) * NT + ct) * X3P + p) * 64 + lane] = pl[p];
+                for (int p = 0; p < X3P; ++p) act1h[(((Ta >> 1) * NT + ct) * X3P + p) * 64 + lane] = pl[p];
+                split3_pair(mask4(mfma_kgroup(a0, bf[ct + dt], z), pre0), mask4(mfma_kgroup(a1, bf[ct + dt], z), pre1),
+                            s1[ct + dt], pl);
+#pragma unroll
+                for (int p = 0; p < X3P; ++p) act1h[(((Ta >> 1) * NT + ct + dt) * X3P + p) * 64 + lane] = pl[p];
+            } else {
+                split3_pair(relu4(mfma_kgroup(a0, bf[ct], z) + bias0), relu4(mfma_kgroup(a1, bf[ct], z) + bias1), s1[ct], pl);
+#pragma unroll
+                for (int p = 0; p < X3P; ++p) act1h[(((Ta >> 1) * NT + ct) * X3P + p) * 64 + lane] = pl[p];
+            }
         }
     }
     __syncthreads();
@@ -809,8 +887,8 @@ __device__ __forceinline__ void head_trunk_x3(const gp_head_weights& w, const fl
     int vo[NT];
 #pragma unroll
     for (int ct = 0; ct < NT; ++ct) vo[ct] = obj_of_col[ct * 16 + n] * (3 * HID * 4) + 16 * q;
-    f32x4 tpv[TPW], pov[TPW][NT];
-    head_x3_init_load<0, NT, TPW>(RP, RT, vo, wid, lane, tpv, pov);
+    f32x4 tpv[TPW], pov[TPW][NP];
+    head_x3_init_load<0, NT, TPW, NP>(RP, RT, vo, wid, lane, tpv, pov);
 #if X3_EPI_EARLY
     // the epilogue's planes are made before the alias barrier (a wave that finished its stream early does
     // this VALU work while it waits for the last one) and only written after it
@@ -820,9 +898,20 @@ __device__ __forceinline__ void head_trunk_x3(const gp_head_weights& w, const fl
         const int Ta = T2[2 * c];
         const f32x4 bias0 = ld4(&sm.pe2b[16 * Ta + 4 * q]), bias1 = ld4(&sm.pe2b[16 * (Ta + 1) + 4 * q]);
 #pragma unroll
-        for (int ct = 0; ct < NT; ++ct)
-            split3_pair(relu4((acc2[2 * c][ct] + cor2[2 * c][ct]) * u2[ct] + bias0),
-                        relu4((acc2[2 * c + 1][ct] + cor2[2 * c + 1][ct]) * u2[ct] + bias1), s2[ct], pls[c][ct]);
+        for (int ct = 0; ct < NP; ++ct) {
+            if constexpr (JVP) {
+                constexpr int dt = JVP ? NP : 0;
+                const f32x4 pre0 = (acc2[2 * c][ct] + cor2[2 * c][ct]) * u2[ct] + bias0;
+                const f32x4 pre1 = (acc2[2 * c + 1][ct] + cor2[2 * c + 1][ct]) * u2[ct] + bias1;
+                split3_pair(relu4(pre0), relu4(pre1), s2[ct], pls[c][ct]);
+                split3_pair(mask4((acc2[2 * c][ct + dt] + cor2[2 * c][ct + dt]) * u2[ct + dt], pre0),
+                            mask4((acc2[2 * c + 1][ct + dt] + cor2[2 * c + 1][ct + dt]) * u2[ct + dt], pre1),
+                            s2[ct + dt], pls[c][ct + dt]);
+            } else {
+                split3_pair(relu4((acc2[2 * c][ct] + cor2[2 * c][ct]) * u2[ct] + bias0),
+                            relu4((acc2[2 * c + 1][ct] + cor2[2 * c + 1][ct]) * u2[ct] + bias1), s2[ct], pls[c][ct]);
+            }
+        }
     }
     if constexpr (SM::kAliasAct) __syncthreads();   // act2 overwrites act1: all reads done
 #pragma unroll
@@ -838,12 +927,26 @@ __device__ __forceinline__ void head_trunk_x3(const gp_head_weights& w, const fl
         const int Ta = T2[2 * c];
         const f32x4 bias0 = ld4(&sm.pe2b[16 * Ta + 4 * q]), bias1 = ld4(&sm.pe2b[16 * (Ta + 1) + 4 * q]);
 #pragma unroll
-        for (int ct = 0; ct < NT; ++ct) {
+        for (int ct = 0; ct < NP; ++ct) {
             f16x8 pl[X3P];
-            split3_pair(relu4((acc2[2 * c][ct] + cor2[2 * c][ct]) * u2[ct] + bias0),
-                        relu4((acc2[2 * c + 1][ct] + cor2[2 * c + 1][ct]) * u2[ct] + bias1), s2[ct], pl);
+            if constexpr (!JVP) {
+                split3_pair(relu4((acc2[2 * c][ct] + cor2[2 * c][ct]) * u2[ct] + bias0),
+                            relu4((acc2[2 * c + 1][ct] + cor2[2 * c + 1][ct]) * u2[ct] + bias1), s2[ct], pl);
 #pragma unroll
-            for (int p = 0; p < X3P; ++p) act2h[(((Ta >> 1) * NT + ct) * X3P + p) * 64 + lane] = pl[p];
+                for (int p = 0; p < X3P; ++p) act2h[(((Ta >> 1) * NT + ct) * X3P + p) * 64 + lane] = pl[p];
+            } else {
+                constexpr int dt = JVP ? NP : 0;
+                const f32x4 pre0 = (acc2[2 * c][ct] + cor2[2 * c][ct]) * u2[ct] + bias0;
+                const f32x4 pre1 = (acc2[2 * c + 1][ct] + cor2[2 * c + 1][ct]) * u2[ct] + bias1;
+                split3_pair(relu4(pre0), relu4(pre1), s2[ct], pl);
+#pragma unroll
+                for (int p = 0; p < X3P; ++p) act2h[(((Ta >> 1) * NT + ct) * X3P + p) * 64 + lane] = pl[p];
+                split3_pair(mask4((acc2[2 * c][ct + dt] + cor2[2 * c][ct + dt]) * u2[ct + dt], pre0),
+                            mask4((acc2[2 * c + 1][ct + dt] + cor2[2 * c + 1][ct + dt]) * u2[ct + dt], pre1),
+                            s2[ct + dt], pl);
+#pragma unroll
+                for (int p = 0; p < X3P; ++p) act2h[(((Ta >> 1) * NT + ct + dt) * X3P + p) * 64 + lane] = pl[p];
+            }
         }
     }
 #endif
@@ -857,29 +960,29 @@ __device__ __forceinline__ void head_trunk_x3(const gp_head_weights& w, const fl
     // timing diagnostic: one wave per SIMD runs head layer 1 for its own output tiles and its sibling's (same
     // results), the sibling idles -- the single-wave stream rate inside the kernel
     if (wid < WV / 2) {
-        head_x3_head<0, NT, WV, TPW, DH>(WH, act2h, RP, RT, vo, sm, uh, sh, wid, lane, ringh, tpv, pov, pv);
+        head_x3_head<0, NT, WV, TPW, DH, JVP>(WH, act2h, RP, RT, vo, sm, uh, sh, wid, lane, ringh, tpv, pov, pv);
         PC_MARK(13);
-        head_x3_head<1, NT, WV, TPW, DH>(WH, act2h, RP, RT, vo, sm, uh, sh, wid, lane, ringh, tpv, pov, pv);
+        head_x3_head<1, NT, WV, TPW, DH, JVP>(WH, act2h, RP, RT, vo, sm, uh, sh, wid, lane, ringh, tpv, pov, pv);
         PC_MARK(14);
-        head_x3_head<2, NT, WV, TPW, DH>(WH, act2h, RP, RT, vo, sm, uh, sh, wid, lane, ringh, tpv, pov, pv);
+        head_x3_head<2, NT, WV, TPW, DH, JVP>(WH, act2h, RP, RT, vo, sm, uh, sh, wid, lane, ringh, tpv, pov, pv);
         const int vw = wid + WV / 2;
         int TV[TPW];
 #pragma unroll
         for (int t = 0; t < TPW; ++t) TV[t] = vw * TPW + t;
         stream_x3_step<0, DH, TPW, NT, DH>(WH, TV, act2h, lane, voff, ringh, acc2, cor2);
-        head_x3_init_load<0, NT, TPW>(RP, RT, vo, vw, lane, tpv, pov);
-        head_x3_head<0, NT, WV, TPW, DH>(WH, act2h, RP, RT, vo, sm, uh, sh, vw, lane, ringh, tpv, pov, pv);
-        head_x3_head<1, NT, WV, TPW, DH>(WH, act2h, RP, RT, vo, sm, uh, sh, vw, lane, ringh, tpv, pov, pv);
-        head_x3_head<2, NT, WV, TPW, DH>(WH, act2h, RP, RT, vo, sm, uh, sh, vw, lane, ringh, tpv, pov, pv);
+        head_x3_init_load<0, NT, TPW, NP>(RP, RT, vo, vw, lane, tpv, pov);
+        head_x3_head<0, NT, WV, TPW, DH, JVP>(WH, act2h, RP, RT, vo, sm, uh, sh, vw, lane, ringh, tpv, pov, pv);
+        head_x3_head<1, NT, WV, TPW, DH, JVP>(WH, act2h, RP, RT, vo, sm, uh, sh, vw, lane, ringh, tpv, pov, pv);
+        head_x3_head<2, NT, WV, TPW, DH, JVP>(WH, act2h, RP, RT, vo, sm, uh, sh, vw, lane, ringh, tpv, pov, pv);
     }
 #else
-    head_x3_head<0, NT, WV, TPW, DH>(WH, act2h, RP, RT, vo, sm, uh, sh, wid, lane, ringh, tpv, pov, pv);
+    head_x3_head<0, NT, WV, TPW, DH, JVP>(WH, act2h, RP, RT, vo, sm, uh, sh, wid, lane, ringh, tpv, pov, pv);
     if constexpr (X3_HEAD_BARRIER) __syncthreads();
     PC_MARK(13);
-    head_x3_head<1, NT, WV, TPW, DH>(WH, act2h, RP, RT, vo, sm, uh, sh, wid, lane, ringh, tpv, pov, pv);
+    head_x3_head<1, NT, WV, TPW, DH, JVP>(WH, act2h, RP, RT, vo, sm, uh, sh, wid, lane, ringh, tpv, pov, pv);
     if constexpr (X3_HEAD_BARRIER) __syncthreads();
     PC_MARK(14);
-    head_x3_head<2, NT, WV, TPW, DH>(WH, act2h, RP, RT, vo, sm, uh, sh, wid, lane, ringh, tpv, pov, pv);
+    head_x3_head<2, NT, WV, TPW, DH, JVP>(WH, act2h, RP, RT, vo, sm, uh, sh, wid, lane, ringh, tpv, pov, pv);
 #endif
     if constexpr (X3_PRIO) __builtin_amdgcn_s_setprio(0);
     PC_MARK(5);

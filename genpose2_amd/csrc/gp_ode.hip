@@ -255,6 +255,138 @@ static int ode_nwg(const gp_head_weights* w, int rows) {
     return (rows + 16 * nt - 1) / (16 * nt);
 }
 
+// ============================================================================ likelihood stages
+// cond_ode_likelihood (samplers.py:25-110): the augmented state y = [x (9R) | logp (R)] (scipy's flat layout),
+// d logp_r / dt = coef * eps_r . (d score_r / d x_r) eps_r with the constant direction eps (R,9). A workgroup
+// holds NP primal column tiles and their NP tangent tiles (the JVP trunk, gp_head.h): entry o < 9 of row r is
+// x_r[o] at y[9 r + o], entry 9 is logp_r at y[9 R + r]. Otherwise ode_stage_body: same stage combination, same
+// error terms (over all ten entries of a row), same fixed summation order of the workgroup partial.
+template <int MODE, int PL, int NP>
+__global__ __launch_bounds__(EVAL_WV * 64) void like_stage_kernel(OdeStageArgs a, const float* __restrict__ eps) {
+    constexpr int NT = 2 * NP;
+    constexpr int ROWS = 16 * NP;     // rows (candidates) of this workgroup
+    constexpr int NTH = EVAL_WV * 64;
+    constexpr bool SPLIT = PL != 0;
+    __shared__ HeadSmem<NT, EVAL_WV, PL> sm;
+    __shared__ int obj[2 * ROWS];
+    __shared__ double y0s[ROWS * 10], y1s[ROWS * 10], esq[EVAL_WV];
+    SplitScalars hs = {};
+    if constexpr (SPLIT) hs = load_split_scalars(a.w);
+    const int tid = threadIdx.x;
+    const int r0 = blockIdx.x * ROWS;
+    const double h = a.h;
+    const size_t n9 = (size_t)a.rows * 9;
+    stage_small_weights<NT, EVAL_WV, 0, !SPLIT>(a.w, sm);
+    // y_in = y + (sum_{j<nk} a_j K_j) h of entry e (ode_stage_body's expression)
+    auto stage_in = [&](size_t e, double yv) {
+#pragma clang fp contract(off)
+        double yi = yv;
+        if (a.nk > 0) {
+            double acc = a.k[0][e] * a.a[0];
+            for (int s = 1; s < a.nk; ++s) acc = acc + a.k[s][e] * a.a[s];
+            yi = yv + acc * h;
+        }
+        return yi;
+    };
+    for (int i = tid; i < 2 * ROWS * 16; i += NTH) {
+        const int c = i >> 4, j = i & 15;
+        float xv = 0.f;
+        if (c < ROWS) {
+            const int r = r0 + c;
+            if (r < a.rows && j < 9) {
+                const size_t e = (size_t)r * 9 + j;
+                const double yv = a.y[e];
+                const double yi = stage_in(e, yv);
+                xv = (float)yi;   // torch.tensor(x, dtype=torch.float32) (samplers.py:83)
+                if (MODE == 1) {
+                    y0s[c * 10 + j] = yv;
+                    y1s[c * 10 + j] = yi;
+                    a.ynew[e] = yi;
+                }
+            }
+        } else {
+            const int r = r0 + c - ROWS;
+            if (r < a.rows && j < 9) xv = eps[(size_t)r * 9 + j];
+        }
+        sm.xin[i] = xv;
+    }
+    if (MODE == 1 && tid < ROWS && r0 + tid < a.rows) {   // logp: not an input of the RHS, only of y_new and the error
+        const size_t e = n9 + (size_t)(r0 + tid);
+        const double yv = a.y[e];
+        const double yi = stage_in(e, yv);
+        y0s[tid * 10 + 9] = yv;
+        y1s[tid * 10 + 9] = yi;
+        a.ynew[e] = yi;
+    }
+    if (tid < 2 * ROWS) {
+        const int r = r0 + (tid < ROWS ? tid : tid - ROWS);
+        obj[tid] = (r < a.rows ? r : a.rows - 1) / a.kper;
+    }
+    if constexpr (SPLIT)
+        head_trunk_x3<NT, EVAL_WV, false, true>(a.w, a.pobj, a.tproj, obj, sm, 0, hs);
+    else
+        head_trunk<NT, EVAL_WV, true>(a.w, a.pobj, a.tproj, obj, sm);
+    double sq = 0.0;   // this thread's (err/scale)^2 terms, its elements in increasing order
+    const float den = fadd(a.sigma, 1e-7f);
+    for (int e10 = tid; e10 < ROWS * 10; e10 += NTH) {
+#pragma clang fp contract(off)
+        const int c = e10 / 10, o = e10 - c * 10;
+        const int r = r0 + c;
+        if (r < a.rows) {
+            const size_t e = o < 9 ? (size_t)r * 9 + o : n9 + (size_t)r;
+            float s;
+            if (o < 9) {
+                s = fdiv(head_out(sm, c, o), den);
+            } else {   // eps . (J eps): nine fp32 products, each rounded on its own, summed in order
+                s = 0.f;
+#pragma unroll
+                for (int j = 0; j < 9; ++j)
+                    s = fadd(s, fmul(ld1(&sm.xin[(ROWS + c) * 16 + j]), fdiv(head_out_tan(sm, ROWS + c, j), den)));
+            }
+            const double kv = a.coef * (double)s;
+            a.kout[e] = kv;
+            if (MODE == 1) {
+                double acc = a.k[0][e] * a.e[0];
+                for (int s2 = 1; s2 < ODE_NK - 1; ++s2) acc = acc + a.k[s2][e] * a.e[s2];
+                acc = acc + kv * a.e[ODE_NK - 1];
+                const double y0 = y0s[e10], y1 = y1s[e10];
+                const double sc = a.atol + fmax(fabs(y0), fabs(y1)) * a.rtol;
+                const double er = (acc * h) / sc;
+                sq += er * er;
+            }
+        }
+    }
+    if (MODE == 1) {
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) sq += __shfl_xor(sq, off, 64);
+        if ((tid & 63) == 0) esq[tid >> 6] = sq;
+        __syncthreads();
+        if (tid == 0) {
+            double t = 0.0;
+            for (int v = 0; v < EVAL_WV; ++v) t += esq[v];
+            a.part[blockIdx.x] = t;
+        }
+    }
+}
+
+// Primal column tiles per workgroup of the likelihood stages: a workgroup streams the GEMM weights once for its
+// primal and tangent tiles together, so the split trunk takes two primal tiles (the 64-column workgroup of the
+// sampler's widest tiling) once 16-row workgroups no longer fit one pass of the CUs.
+static int like_np(const gp_head_weights* w, int rows) {
+    return (w->pe2_h != nullptr && rows >= PC_SPLIT_NT2_MIN) ? 2 : 1;
+}
+
+template <int MODE>
+static void like_launch_stage(const OdeStageArgs& a, const float* eps, int np, hipStream_t st) {
+    const dim3 grid((a.rows + 16 * np - 1) / (16 * np)), blk(EVAL_WV * 64);
+    if (!a.w.pe2_h)
+        hipLaunchKernelGGL((like_stage_kernel<MODE, 0, 1>), grid, blk, 0, st, a, eps);
+    else if (np == 2)
+        hipLaunchKernelGGL((like_stage_kernel<MODE, X3P, 2>), grid, blk, 0, st, a, eps);
+    else
+        hipLaunchKernelGGL((like_stage_kernel<MODE, X3P, 1>), grid, blk, 0, st, a, eps);
+}
+
 // Sum of part[0..n) by a 256-thread workgroup in a fixed order (strided per-thread sums, xor
 // shuffles within each wave, the four wave sums in wave order): every caller that reduces the same
 // partials gets the same bits. `red` is 4 doubles of LDS.
@@ -572,6 +704,90 @@ extern "C" int gp_ode_attempt(const gp_head_weights* w, const float* pobj, const
     hipLaunchKernelGGL(ode_norm_kernel, dim3(1), dim3(256), 0, stream, (const double*)part, nwg,
                        (double)rows * 9.0, err_out);
     return gp_check_launch("ode_stage_kernel<final>");
+}
+
+// ------------------------------------------------------------------------------ likelihood (host-controlled)
+// Workspace as the sampler's: 6 time rows | one error partial per 16 rows (an upper bound for every tiling).
+extern "C" size_t gp_like_workspace_size(int rows) { return gp_ode_workspace_size(rows); }
+
+extern "C" int gp_like_rhs(const gp_head_weights* w, const float* pobj, float t32, float sigma, double coef,
+                           const double* y, const float* eps, const double* const* kin, const double* acoef, int nk,
+                           double h, int rows, int k, double* kout, void* workspace, size_t workspace_bytes,
+                           hipStream_t stream) {
+    GP_REQUIRE(w && pobj && y && eps && kout && workspace && rows >= 1 && k >= 1, "like_rhs: bad arguments");
+    GP_REQUIRE(nk >= 0 && nk < ODE_NK && (nk == 0 || (kin && acoef)), "like_rhs: nk must be in [0, 6]");
+    GP_REQUIRE(workspace_bytes >= gp_like_workspace_size(rows), "like_rhs: workspace too small");
+    OdeStageArgs a = {};
+    a.w = *w;
+    a.pobj = pobj;
+    a.tproj = static_cast<const float*>(workspace);
+    a.sigma = sigma;
+    a.coef = coef;
+    a.y = y;
+    for (int j = 0; j < nk; ++j) {
+        GP_REQUIRE(kin[j] != nullptr, "like_rhs: null stage pointer");
+        a.k[j] = kin[j];
+        a.a[j] = acoef[j];
+    }
+    a.nk = nk;
+    a.h = h;
+    a.kout = kout;
+    a.rows = rows;
+    a.kper = k;
+    int rc = ode_launch_times(w, &t32, 1, workspace, stream);
+    if (rc) return rc;
+    like_launch_stage<0>(a, eps, like_np(w, rows), stream);
+    return gp_check_launch("like_stage_kernel");
+}
+
+extern "C" int gp_like_attempt(const gp_head_weights* w, const float* pobj, const float* t32_6, const float* sigma_6,
+                               const double* coef_6, const double* y, const float* eps, double* const* kslots,
+                               const double* tableau_a, const double* b, const double* e, double h, double rtol,
+                               double atol, int rows, int k, double* ynew, double* err_out, void* workspace,
+                               size_t workspace_bytes, hipStream_t stream) {
+    GP_REQUIRE(w && pobj && t32_6 && sigma_6 && coef_6 && y && eps && kslots && tableau_a && b && e && ynew &&
+                   err_out && workspace && rows >= 1 && k >= 1,
+               "like_attempt: bad arguments");
+    GP_REQUIRE(workspace_bytes >= gp_like_workspace_size(rows), "like_attempt: workspace too small");
+    for (int j = 0; j < ODE_NK; ++j) GP_REQUIRE(kslots[j] != nullptr, "like_attempt: null K slot");
+    const int np = like_np(w, rows);
+    const int nwg = (rows + 16 * np - 1) / (16 * np);
+    const float* tproj = static_cast<const float*>(workspace);
+    double* part = reinterpret_cast<double*>(static_cast<char*>(workspace) + ode_part_offset());
+    int rc = ode_launch_times(w, t32_6, 6, workspace, stream);
+    if (rc) return rc;
+    OdeStageArgs a = {};
+    a.w = *w;
+    a.pobj = pobj;
+    a.y = y;
+    a.h = h;
+    a.rows = rows;
+    a.kper = k;
+    a.rtol = rtol;
+    a.atol = atol;
+    for (int j = 0; j < ODE_NK; ++j) a.k[j] = kslots[j];
+    for (int s = 1; s < 6; ++s) {
+        a.tproj = tproj + (size_t)(s - 1) * 768;
+        a.sigma = sigma_6[s - 1];
+        a.coef = coef_6[s - 1];
+        a.nk = s;
+        for (int j = 0; j < s; ++j) a.a[j] = tableau_a[s * 6 + j];
+        a.kout = kslots[s];
+        like_launch_stage<0>(a, eps, np, stream);
+    }
+    a.tproj = tproj + (size_t)5 * 768;
+    a.sigma = sigma_6[5];
+    a.coef = coef_6[5];
+    a.nk = 6;
+    for (int j = 0; j < 6; ++j) a.a[j] = b[j];
+    for (int j = 0; j < ODE_NK; ++j) a.e[j] = e[j];
+    a.kout = kslots[6];
+    a.ynew = ynew;
+    a.part = part;
+    like_launch_stage<1>(a, eps, np, stream);
+    hipLaunchKernelGGL(ode_norm_kernel, dim3(1), dim3(256), 0, stream, (const double*)part, nwg,
+                       (double)rows * 10.0, err_out);
+    return gp_check_launch("like_stage_kernel<final>");
 }
 
 extern "C" int gp_ode_init_norms(const double* y0, const double* f0, const double* f1, long long n, double atol,

@@ -154,6 +154,66 @@ extern "C" int gp_score_eval(const gp_head_weights* w, const float* pobj, const 
     return gp_check_launch("head_eval_kernel<score>");
 }
 
+// Score and eps . (d score / d x) eps of 16 rows per workgroup: column tile 0 carries the poses, column tile 1
+// their tangents (the JVP trunk, gp_head.h). div sums the nine products in fp32, in order, each rounded on its
+// own (the reference's torch.sum(grad * epsilon, dim=-1) is fp32 too).
+template <int PL>
+__global__ __launch_bounds__(EVAL_WV * 64) void head_div_eval_kernel(gp_head_weights w, const float* __restrict__ pobj,
+                                                       const float* __restrict__ tproj, float sigma,
+                                                       const float* __restrict__ x, const float* __restrict__ eps,
+                                                       int rows, int kper, float* __restrict__ score,
+                                                       float* __restrict__ div) {
+    __shared__ HeadSmem<2, EVAL_WV, PL> sm;
+    constexpr bool SPLIT = PL != 0;
+    __shared__ int obj[32];
+    const int r0 = blockIdx.x * 16;
+    SplitScalars hs = {};
+    if constexpr (SPLIT) hs = load_split_scalars(w);
+    stage_small_weights<2, EVAL_WV, 0, !SPLIT>(w, sm);
+    for (int i = threadIdx.x; i < 512; i += EVAL_WV * 64) {
+        const int c = i >> 4, j = i & 15;
+        const int r = r0 + (c & 15);
+        const float* src = c < 16 ? x : eps;
+        sm.xin[i] = (r < rows && j < 9) ? src[(size_t)r * 9 + j] : 0.f;
+    }
+    if (threadIdx.x < 32) {
+        const int r = r0 + (threadIdx.x & 15);
+        obj[threadIdx.x] = (r < rows ? r : rows - 1) / kper;
+    }
+    if constexpr (SPLIT)
+        head_trunk_x3<2, EVAL_WV, false, true>(w, pobj, tproj, obj, sm, 0, hs);
+    else
+        head_trunk<2, EVAL_WV, true>(w, pobj, tproj, obj, sm);
+    if (threadIdx.x < 160) {
+        const int c = threadIdx.x / 10, o = threadIdx.x - c * 10;
+        if (r0 + c < rows) {
+            const float den = fadd(sigma, 1e-7f);
+            if (o < 9) {
+                score[(size_t)(r0 + c) * 9 + o] = fdiv(head_out(sm, c, o), den);
+            } else {
+                float d = 0.f;
+#pragma unroll
+                for (int j = 0; j < 9; ++j) d = fadd(d, fmul(ld1(&sm.xin[(16 + c) * 16 + j]), fdiv(head_out_tan(sm, 16 + c, j), den)));
+                div[r0 + c] = d;
+            }
+        }
+    }
+}
+
+extern "C" int gp_score_div_eval(const gp_head_weights* w, const float* pobj, const float* tproj_row, float sigma,
+                                 const float* x, const float* eps, int rows, int k, float* score, float* div,
+                                 hipStream_t stream) {
+    GP_REQUIRE(w && pobj && tproj_row && x && eps && score && div && rows >= 0 && k >= 1, "score_div_eval: bad arguments");
+    if (!rows) return GP_OK;
+    if (w->pe2_h)
+        hipLaunchKernelGGL((head_div_eval_kernel<X3P>), dim3((rows + 15) / 16), dim3(EVAL_WV * 64), 0, stream, *w, pobj,
+                           tproj_row, sigma, x, eps, rows, k, score, div);
+    else
+        hipLaunchKernelGGL((head_div_eval_kernel<0>), dim3((rows + 15) / 16), dim3(EVAL_WV * 64), 0, stream, *w, pobj,
+                           tproj_row, sigma, x, eps, rows, k, score, div);
+    return gp_check_launch("head_div_eval_kernel");
+}
+
 extern "C" int gp_energy_eval(const gp_head_weights* w, const float* pobj, const float* tproj_row, float sigma,
                               const float* pose, int rows, int k, float* energy, hipStream_t stream) {
     GP_REQUIRE(w && pobj && tproj_row && pose && energy && rows >= 0 && k >= 1, "energy_eval: bad arguments");

@@ -258,6 +258,22 @@ class HeadModel:
                                      self._s()), "score_eval")
         return out
 
+    def score_div(self, pobj, tproj_row, sigma: float, x: torch.Tensor, eps: torch.Tensor, k: int):
+        """gp_score_div_eval: score (R,9) and div (R) = eps . (d score / d x) eps per row (forward mode), fp32."""
+        x = require_device_tensor(x, "x")
+        eps = require_device_tensor(eps, "eps")
+        R = x.shape[0]
+        if tuple(eps.shape) != (R, arch.POSE_DIM):
+            raise ValueError(f"eps must be ({R}, {arch.POSE_DIM}), got {tuple(eps.shape)}")
+        score = torch.empty((R, arch.POSE_DIM), dtype=torch.float32, device=self.device)
+        div = torch.empty((R,), dtype=torch.float32, device=self.device)
+        check(self.lib.gp_score_div_eval(ctypes.byref(self.w), ctypes.c_void_p(pobj.data_ptr()),
+                                         ctypes.c_void_p(tproj_row.data_ptr()), ctypes.c_float(sigma),
+                                         ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(eps.data_ptr()), R, k,
+                                         ctypes.c_void_p(score.data_ptr()), ctypes.c_void_p(div.data_ptr()),
+                                         self._s()), "score_div_eval")
+        return score, div
+
     def energy(self, pobj, tproj_row, sigma: float, pose: torch.Tensor, k: int) -> torch.Tensor:
         pose = require_device_tensor(pose, "pose")
         R = pose.shape[0]

@@ -394,6 +394,58 @@ class DeviceRk45:
         return torch.stack(self.ys, 0)
 
 
+class LikelihoodRk45(DeviceRk45):
+    """cond_ode_likelihood's solve (samplers.py:77-99) as an rk45_drive backend: the augmented state
+    y = [x.reshape(-1) (9R) | logp (R)] (init_logp = 0), K_0..K_6 and y_new as fp64 device tensors of 10 R
+    entries; a right-hand side is one gp_like_rhs launch (score and eps . (d score / d x) eps in one forward-mode
+    pass), an attempt gp_like_attempt. Every norm runs over all 10 R entries (gp_ode_init_norms is generic in n).
+    ``eps`` (R,9) fp32: the Skilling-Hutchinson direction, constant over the solve."""
+
+    def __init__(self, heads, pobj: torch.Tensor, x0: torch.Tensor, eps: torch.Tensor, k: int, rtol: float = 1e-5,
+                 atol: float = 1e-5):
+        R = x0.numel() // arch.POSE_DIM
+        dev = heads.device
+        y0 = torch.zeros(R * (arch.POSE_DIM + 1), dtype=torch.float64, device=dev)
+        y0[: R * arch.POSE_DIM] = x0.reshape(-1).to(dev, torch.float64)
+        super().__init__(heads, pobj, y0, k, rtol, atol)
+        self.R = R
+        self.n = R * (arch.POSE_DIM + 1)
+        if tuple(eps.shape) != (R, arch.POSE_DIM):
+            raise ValueError(f"epsilon must be ({R}, {arch.POSE_DIM}), got {tuple(eps.shape)}")
+        self.eps = eps.to(dev, torch.float32).contiguous()
+        self.y = y0
+        self.K = [torch.empty(self.n, dtype=torch.float64, device=dev) for _ in range(N_STAGES + 1)]
+        self.f1 = torch.empty(self.n, dtype=torch.float64, device=dev)
+        self.ws = torch.empty(int(self.lib.gp_like_workspace_size(R)), dtype=torch.uint8, device=dev)
+
+    def _rhs(self, t, kin, acoef, h, kout):
+        t32, sig, coef = time_scalars(t)
+        nk = len(kin)
+        karr = _ptr_array(kin) if nk else None
+        aarr = (ctypes.c_double * nk)(*acoef) if nk else None
+        check(self.lib.gp_like_rhs(ctypes.byref(self.h.w), ctypes.c_void_p(self.pobj.data_ptr()), t32, sig, coef,
+                                   ctypes.c_void_p(self.y.data_ptr()), ctypes.c_void_p(self.eps.data_ptr()), karr,
+                                   aarr, nk, float(h), self.R, self.k, ctypes.c_void_p(kout.data_ptr()),
+                                   ctypes.c_void_p(self.ws.data_ptr()), self.ws.numel(), self._s()), "like_rhs")
+
+    def attempt(self, t, h):
+        stage_t = [t + c * h for c in C[1:]] + [t + h]
+        t32, sig, coef = stage_scalars(stage_t)
+        self.y_new = torch.empty(self.n, dtype=torch.float64, device=self.dev)
+        check(self.lib.gp_like_attempt(
+            ctypes.byref(self.h.w), ctypes.c_void_p(self.pobj.data_ptr()), t32.ctypes.data_as(ctypes.c_void_p),
+            sig.ctypes.data_as(ctypes.c_void_p), coef.ctypes.data_as(ctypes.c_void_p),
+            ctypes.c_void_p(self.y.data_ptr()), ctypes.c_void_p(self.eps.data_ptr()), _ptr_array(self.K),
+            _A6.ctypes.data_as(ctypes.c_void_p), _B6.ctypes.data_as(ctypes.c_void_p),
+            _E7.ctypes.data_as(ctypes.c_void_p), float(h), self.rtol, self.atol, self.R, self.k,
+            ctypes.c_void_p(self.y_new.data_ptr()), ctypes.c_void_p(self.scal[3:].data_ptr()),
+            ctypes.c_void_p(self.ws.data_ptr()), self.ws.numel(), self._s()), "like_attempt")
+        return self.scal[3:4].cpu().numpy()[0]
+
+    def set_t_eval(self, t_eval, direction, keep_all):
+        raise NotImplementedError("the likelihood solve has no t_eval (samplers.py:97-99)")
+
+
 class GlobalDeviceRk45(DeviceRk45):
     """DeviceRk45 for one shard of a global-batch solve (shard.GlobalBatch ``gb``: this rank holds the rows of
     objects [gb.lo, gb.hi), K each, of one solve_ivp call on the whole batch). select_initial_step's norms are

@@ -225,6 +225,15 @@ int gp_head_time_proj(const gp_head_weights *w, const float *t, int nt, float *t
 int gp_score_eval(const gp_head_weights *w, const float *pobj, const float *tproj_row,
                   float sigma, const float *x, int rows, int k, float *score, hipStream_t stream);
 
+/* Score and its directional divergence term in one forward-mode pass (cond_ode_likelihood's
+ * divergence_eval, samplers.py:54-68, without a backward pass): score (R,9) as gp_score_eval, and
+ * div (R) = sum_o eps[r][o] (J_r eps_r)[o] with J_r = d score_r / d x_r, the Skilling-Hutchinson
+ * estimate for the direction eps (R,9). The tangent J eps runs through the same GEMMs next to the
+ * primal on shared weight fragments, with the primal's ReLU masks (relu' = 0 at 0). */
+int gp_score_div_eval(const gp_head_weights *w, const float *pobj, const float *tproj_row,
+                      float sigma, const float *x, const float *eps, int rows, int k, float *score,
+                      float *div, hipStream_t stream);
+
 /* Energy (IP / score / identical, decoupled rot-trans): pose rows (R,9) with translation
  * already relative to pts_center -> energy (R,2). t is a single value with its tproj row. */
 int gp_energy_eval(const gp_head_weights *w, const float *pobj, const float *tproj_row,
@@ -319,6 +328,23 @@ int gp_ode_attempt(const gp_head_weights *w, const float *pobj, const float *t32
  * f1 == NULL -> out[0] = rms(y0/scale), out[1] = rms(f0/scale); else out[2] = rms((f1-f0)/scale). */
 int gp_ode_init_norms(const double *y0, const double *f0, const double *f1, long long n,
                       double atol, double rtol, double *out, hipStream_t stream);
+/* Pose log-likelihood (cond_ode_likelihood, samplers.py:25-110): the same ODE over the augmented
+ * state y = [x.reshape(-1) (9R) | logp (R)] (scipy's flat layout), d logp_r / dt = coef * div_r with
+ * div of gp_score_div_eval for the constant direction eps (R,9) fp32 and the same coef as x (the VE
+ * drift is 0). y, K_0..K_6 and y_new are fp64 arrays of 10 R entries; error norms run over all 10 R
+ * (gp_ode_init_norms with n = 10 R serves select_initial_step). gp_like_rhs / gp_like_attempt take
+ * the arguments of gp_ode_rhs / gp_ode_attempt plus eps, and need gp_like_workspace_size(rows)
+ * bytes of workspace. */
+size_t gp_like_workspace_size(int rows);
+int gp_like_rhs(const gp_head_weights *w, const float *pobj, float t32, float sigma, double coef,
+                const double *y, const float *eps, const double *const *kin, const double *acoef,
+                int nk, double h, int rows, int k, double *kout, void *workspace,
+                size_t workspace_bytes, hipStream_t stream);
+int gp_like_attempt(const gp_head_weights *w, const float *pobj, const float *t32_6,
+                    const float *sigma_6, const double *coef_6, const double *y, const float *eps,
+                    double *const *kslots, const double *tableau_a, const double *b, const double *e,
+                    double h, double rtol, double atol, int rows, int k, double *ynew,
+                    double *err_out, void *workspace, size_t workspace_bytes, hipStream_t stream);
 /* Dense output of an accepted step (scipy RkDenseOutput): for i in [i0, i1),
  * x = (t_eval[i] - t_old)/h, out[row] = h * (K^T P) cumprod([x,x,x,x]) + y_old with
  * row = reverse ? i_base - i : i - i_base. P7x4 (HOST 7x4), kslots (HOST, 7 device pointers). */
