@@ -28,6 +28,10 @@ class HeadWeights(ctypes.Structure):
                                        "hsc")]
 
 
+class HeadGradWeights(ctypes.Structure):
+    _fields_ = [(n, c_void_p) for n in ("pe0_wt", "pe2_wt", "h1p_wt")]
+
+
 class ScaleWeights(ctypes.Structure):
     _fields_ = [(n, c_void_p) for n in ("ae0_w", "ae0_b", "ae2_w", "ae2_b", "ft0_w", "ft0_b", "ft2_w",
                                        "ft2_b")]
@@ -85,6 +89,13 @@ _SIGS: Dict[str, tuple] = {
                               c_void_p, c_void_p]),
     "gp_energy_eval": (c_int, [ctypes.POINTER(HeadWeights), c_void_p, c_void_p, c_float, c_void_p, c_int, c_int,
                                c_void_p, c_void_p]),
+    "gp_head_grad_floats": (c_size_t, []),
+    "gp_head_grad_pack": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gp_energy_score_eval": (c_int, [ctypes.POINTER(HeadWeights), ctypes.POINTER(HeadGradWeights), c_void_p, c_void_p,
+                                     c_float, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "gp_pc_sample_energy": (c_int, [ctypes.POINTER(HeadWeights), ctypes.POINTER(HeadGradWeights), c_void_p, c_void_p,
+                                    c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_uint64,
+                                    c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "gp_pc_workspace_size": (c_size_t, [c_int]),
     "gp_pc_tile_rows": (c_int, [c_int, c_int]),
     "gp_pc_sample": (c_int, [ctypes.POINTER(HeadWeights), c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int,

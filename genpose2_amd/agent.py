@@ -218,8 +218,14 @@ class PoseNet:
         """posenet_agent.py:490-584. extract_feature=False takes data["pts_feat"] from an earlier
         encode_func (as get_energy's flag does), so a serving loop can encode the next batch on a
         side stream while this one samples."""
-        if self.cfg.agent_type != "score":
-            raise NotImplementedError("pred_func needs agent_type='score'")
+        if self.cfg.agent_type not in ("score", "energy"):
+            raise NotImplementedError("pred_func needs agent_type='score' or 'energy'")
+        energy_grad = self.cfg.agent_type == "energy"   # the score is the energy's gradient (energynet.py:211-233)
+        if energy_grad and self.cfg.sampler_mode[0] == "ode":
+            raise NotImplementedError("the ODE sampler is not built for agent_type='energy' (the energy gradient "
+                                      "drives the PC sampler only)")
+        if energy_grad and self.global_batch is not None:
+            raise NotImplementedError("global-batch sampling is not built for agent_type='energy'")
         self.is_testing = True
         feat = self._encode(data) if extract_feature else dev.require_device_tensor(data["pts_feat"], "pts_feat")
         data["pts_feat"] = feat
@@ -254,7 +260,7 @@ class PoseNet:
             seed = (self.cfg.noise_seed * 1000003 + self._calls) & 0xFFFFFFFFFFFF
             want_xs = bool(return_process or self.cfg.save_video)
             res, q, xs = self.heads.pc_sample(pobj, tproj, tab, x, K, center, z1, z2, seed=seed, want_xs=want_xs,
-                                              global_batch=gb)
+                                              global_batch=gb, energy_grad=energy_grad)
             pred_pose = res.view(bs, K, -1)
             pred_q = q.view(bs, K, -1)
             in_process = xs.view(bs, K, T, -1) if xs is not None else None

@@ -172,14 +172,29 @@ __device__ __forceinline__ float head_out_tan(const HeadSmem<NT, WV, PL>& sm, in
     return acc;
 }
 
+// Reverse-pass buffers of the energy-gradient kernels (head_trunk<.., GRAD>, head_backward): cotangents in the
+// B-operand layout, [k-group][lane]. g1 (the cotangent of pose_encoder.0's output) takes gh's first 16
+// k-groups and the per-wave partials of the pose gradient take g2's: each is written after a barrier that
+// retires every read of the buffer it reuses.
+struct GradSmem {
+    f32x4 gh[3 * KG_HID * 64];   // cotangent of head layer 1's pre-activations, k-group = head * 16 + tile
+    f32x4 g2[KG_HID * 64];       // cotangent of pose_encoder.2's pre-activations
+};
+
 // Computes the head outputs (read with head_out) for the candidates of this workgroup. Starts with
 // the workgroup barrier that publishes sm.xin, obj_of_col and the staged weights (callers write
 // them before the call without a barrier of their own; the first weight loads are issued before it).
 // `obj_of_col` maps column -> object row of pobj; `tproj` is the 768-vector of this time value.
-template <int NT, int WV, bool JVP = false>
+// GRAD (the energy model's score, grad_x sum_o x_o f_o / sigma): the trunk also leaves the cotangent of head
+// layer 1's pre-activations in gs->gh, gh[h][j] = (pre1[h][j] > 0) ? sum_o h2_w[h][o][j] c[3h+o] : 0 with
+// c = xin / sigma, formed in the lanes that hold pre1 (the accumulator-native layout is head_backward's B
+// operand); act1 and act2 stay live for the reverse pass's masks. The closing barrier is left to
+// head_backward, which primes its first weight ring in front of it.
+template <int NT, int WV, bool JVP = false, bool GRAD = false>
 __device__ __forceinline__ void head_trunk(const gp_head_weights& w, const float* __restrict__ pobj,
                            const float* __restrict__ tproj, const int* obj_of_col, HeadSmem<NT, WV>& sm,
-                           int trace_slot = 0) {
+                           int trace_slot = 0, GradSmem* gs = nullptr, float sigma = 1.f) {
+    static_assert(!GRAD || (NT == 1 && !JVP), "the reverse pass runs one 16-candidate tile");
     constexpr int TPW = 16 / WV;   // output tiles per wave and per 256-wide layer
     constexpr int NP = JVP ? NT / 2 : NT;   // primal column tiles (tangent tile ct pairs with ct - NP)
     static_assert(!JVP || NT % 2 == 0, "a JVP trunk pairs every primal tile with a tangent tile");
@@ -286,6 +301,14 @@ __device__ __forceinline__ void head_trunk(const gp_head_weights& w, const float
     // ---- ReLU -> head layer 2 (block diagonal 3 x (256 -> 3)) partial dot products
 #pragma unroll
     for (int h = 0; h < 3; ++h) {
+        // GRAD: this lane's column of the cotangent c = x / sigma for head h's three outputs, once per head
+        [[maybe_unused]] float c0 = 0.f, c1 = 0.f, c2 = 0.f;
+        if constexpr (GRAD) {
+            // ld1: three consecutive floats, never merged into one 12-byte LDS read (gp_common.h)
+            c0 = fdiv(ld1(&sm.xin[n * 16 + 3 * h + 0]), sigma);
+            c1 = fdiv(ld1(&sm.xin[n * 16 + 3 * h + 1]), sigma);
+            c2 = fdiv(ld1(&sm.xin[n * 16 + 3 * h + 2]), sigma);
+        }
 #pragma unroll
         for (int ct = 0; ct < NT; ++ct) {
             float p0 = 0.f, p1 = 0.f, p2 = 0.f;
@@ -304,6 +327,8 @@ __device__ __forceinline__ void head_trunk(const gp_head_weights& w, const float
                 p0 += u.x * w0.x + u.y * w0.y + u.z * w0.z + u.w * w0.w;
                 p1 += u.x * w1.x + u.y * w1.y + u.z * w1.z + u.w * w1.w;
                 p2 += u.x * w2.x + u.y * w2.y + u.z * w2.z + u.w * w2.w;
+                if constexpr (GRAD)
+                    gs->gh[TH[h * TPW + t] * 64 + lane] = mask4(w0 * c0 + w1 * c1 + w2 * c2, acc[h * TPW + t][ct]);
             }
             p0 = rows_sum(p0);
             p1 = rows_sum(p1);
@@ -315,8 +340,83 @@ __device__ __forceinline__ void head_trunk(const gp_head_weights& w, const float
             }
         }
     }
-    __syncthreads();
+    if constexpr (!GRAD) __syncthreads();
     PC_MARK(6);
+}
+
+#ifndef GRAD_D
+#define GRAD_D 4                 // k-groups of transposed weights kept in flight in the reverse pass
+#endif
+
+// Reverse pass of head_trunk<1, WV, false, true>: J_f^T c for the 16 candidates, from gs.gh back through head
+// layer 1's pose block (h1p_w^T, 256 x 768: 48 k-groups), pose_encoder.2 (pe2_w^T) and pose_encoder.0
+// (pe0_w^T, 9 rows padded to one output tile). The transposed weights are packed like the forward ones
+// (pack_a_fragments of W^T), so stream_step reads them unchanged, and a layer's output tile T is the next
+// layer's k-group T here too. Each ReLU's mask is the forward activation > 0 (act = relu(pre), so the same
+// units as pre > 0), in the same lane and slot. Every layer's first GRAD_D k-groups of weights are issued in
+// front of the barrier that publishes its B operand. The last layer splits K over the waves (two k-groups
+// each); their partial tiles are summed in wave order by pose_grad. Starts with the barrier the GRAD trunk
+// leaves out and ends with the one that publishes the partials.
+template <int WV>
+__device__ __forceinline__ void head_backward(const gp_head_grad_weights& gw, const HeadSmem<1, WV>& sm, GradSmem& gs,
+                                              int trace_slot = 0) {
+    constexpr int TPW = 16 / WV;
+    constexpr int KPW = KG_HID / WV;   // k-groups per wave of the K-split last layer
+    constexpr int D = GRAD_D;
+    static_assert(KPW * WV == KG_HID && WV * 64 <= KG_HID * 64, "the partial tiles fit g2");
+    const int tid = tid_x();
+    const int lane = tid & 63;
+    const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int voff = lane * 16;
+    const __amdgpu_buffer_rsrc_t WH = make_rsrc(gw.h1p_wt, 3 * HID * HID * 4);
+    const __amdgpu_buffer_rsrc_t W2 = make_rsrc(gw.pe2_wt, HID * HID * 4);
+    const __amdgpu_buffer_rsrc_t W0 = make_rsrc(gw.pe0_wt, 16 * HID * 4);
+    int T2[TPW];
+#pragma unroll
+    for (int t = 0; t < TPW; ++t) T2[t] = wid * TPW + t;
+    f32x4 ring[D + 1][TPW];
+    f32x4 acc[TPW][1];
+    // ---- head layer 1, pose block: g2 = mask(act2) . sum_h W1pose_h^T gh_h
+#pragma unroll
+    for (int t = 0; t < TPW; ++t) acc[t][0] = f32x4{0.f, 0.f, 0.f, 0.f};
+    stream_step<0, D, TPW, 1, 3 * KG_HID, D>(WH, T2, gs.gh, lane, voff, ring, acc);
+    __syncthreads();
+    PC_MARK(13);
+    stream_step<D, 3 * KG_HID + D, TPW, 1, 3 * KG_HID, D>(WH, T2, gs.gh, lane, voff, ring, acc);
+#pragma unroll
+    for (int t = 0; t < TPW; ++t) {
+        gs.g2[T2[t] * 64 + lane] = mask4(acc[t][0], sm.act2[T2[t] * 64 + lane]);
+        acc[t][0] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    // ---- pose_encoder.2: g1 = mask(act1) . pe2_w^T g2 (into gh's first 16 k-groups)
+    f32x4* g1 = gs.gh;
+    stream_step<0, D, TPW, 1, KG_HID, D>(W2, T2, gs.g2, lane, voff, ring, acc);
+    __syncthreads();
+    PC_MARK(14);
+    stream_step<D, KG_HID + D, TPW, 1, KG_HID, D>(W2, T2, gs.g2, lane, voff, ring, acc);
+#pragma unroll
+    for (int t = 0; t < TPW; ++t) g1[T2[t] * 64 + lane] = mask4(acc[t][0], sm.act1[T2[t] * 64 + lane]);
+    // ---- pose_encoder.0: this wave's k-groups [KPW wid, KPW wid + KPW) of the one output tile, addressed as
+    //      "tile wid of a KPW-deep layer"
+    const int T0[1] = {wid};
+    f32x4 ring0[KPW + 1][1];
+    f32x4 acc0[1][1] = {{f32x4{0.f, 0.f, 0.f, 0.f}}};
+    stream_step<0, KPW, 1, 1, KPW, KPW>(W0, T0, g1, lane, voff, ring0, acc0);
+    __syncthreads();
+    PC_MARK(15);
+    stream_step<KPW, 2 * KPW, 1, 1, KPW, KPW>(W0, T0, g1 + wid * KPW * 64, lane, voff, ring0, acc0);
+    gs.g2[wid * 64 + lane] = acc0[0][0];
+    __syncthreads();
+}
+
+// (J_f^T c)[o] of column c (valid after head_backward): the waves' partial tiles in wave order. Output row o
+// of the tile sits in lane 16 (o / 4) + c, entry o % 4.
+template <int WV>
+__device__ __forceinline__ float pose_grad(const GradSmem& gs, int c, int o) {
+    float acc = 0.f;
+#pragma unroll
+    for (int w = 0; w < WV; ++w) acc += gs.g2[w * 64 + 16 * (o >> 2) + c][o & 3];
+    return acc;
 }
 
 // ============================================================================ f16 MFMA helpers

@@ -390,6 +390,24 @@ extern "C" int gp_weights_pack(int kind, int n, const char* const* names, const 
     return GP_OK;
 }
 
+// pack.pack_heads_grad: A fragments of the three transposed pose-path layers (the energy gradient's reverse pass)
+extern "C" int gp_head_grad_pack(const float* pe0_w, const float* pe2_w, const float* h1_pose, float* out) {
+    GP_REQUIRE(pe0_w && pe2_w && h1_pose && out, "head_grad_pack: null pointer");
+    auto transposed = [](const float* w, int n_out, int k_in) {   // (n_out, k_in) -> (k_in, n_out)
+        std::vector<float> t((size_t)n_out * k_in);
+        for (int o = 0; o < n_out; ++o)
+            for (int c = 0; c < k_in; ++c) t[(size_t)c * n_out + o] = w[(size_t)o * k_in + c];
+        return t;
+    };
+    const std::vector<float> p0 = pack_a(transposed(pe0_w, 256, 9), 9, 256, 16, 256);
+    const std::vector<float> p2 = pack_a(transposed(pe2_w, 256, 256), 256, 256, 256, 256);
+    const std::vector<float> ph = pack_a(transposed(h1_pose, 768, 256), 256, 768, 256, 768);
+    std::memcpy(out, p0.data(), p0.size() * sizeof(float));
+    std::memcpy(out + p0.size(), p2.data(), p2.size() * sizeof(float));
+    std::memcpy(out + p0.size() + p2.size(), ph.data(), ph.size() * sizeof(float));
+    return GP_OK;
+}
+
 extern "C" void gp_weights_free(gp_weights* w) {
     if (!w) return;
     if (w->dev) (void)hipFree(w->dev);

@@ -227,6 +227,68 @@ extern "C" int gp_energy_eval(const gp_head_weights* w, const float* pobj, const
     return gp_check_launch("head_eval_kernel<energy>");
 }
 
+// ============================================================================ energy gradient
+// The energy model's score (PoseEnergyNet.forward(return_item='score'), energynet.py:211-233) of 16 rows per
+// workgroup: score = grad_x E, E = sum_o x_o f_o / sigma, by the exact-fp32 trunk and its reverse pass
+// (gp_head.h head_backward). score_o = f_o / sigma + (J_f^T c)_o; energy (if asked) sums the nine products in
+// order, each rounded on its own.
+__global__ __launch_bounds__(EVAL_WV * 64) void head_grad_eval_kernel(gp_head_weights w, gp_head_grad_weights gw,
+                                                       const float* __restrict__ pobj,
+                                                       const float* __restrict__ tproj, float sigma,
+                                                       const float* __restrict__ x, int rows, int kper,
+                                                       float* __restrict__ score, float* __restrict__ energy) {
+    __shared__ HeadSmem<1, EVAL_WV, 0> sm;
+    __shared__ GradSmem gs;
+    __shared__ int obj[16];
+    const int r0 = blockIdx.x * 16;
+    stage_small_weights<1, EVAL_WV, 0, true>(w, sm);
+    for (int i = threadIdx.x; i < 256; i += EVAL_WV * 64) {
+        const int c = i >> 4, j = i & 15;
+        const int r = r0 + c;
+        sm.xin[i] = (r < rows && j < 9) ? x[(size_t)r * 9 + j] : 0.f;
+    }
+    if (threadIdx.x < 16) {
+        const int r = r0 + threadIdx.x;
+        obj[threadIdx.x] = (r < rows ? r : rows - 1) / kper;
+    }
+    head_trunk<1, EVAL_WV, false, true>(w, pobj, tproj, obj, sm, 0, &gs, sigma);
+    head_backward<EVAL_WV>(gw, sm, gs);
+    // a lane per (row, output); the products x_o f_o / sigma of the energy go through LDS to the row's first lane.
+    // The head output passes through an opaque copy: fused with pose_grad's sum into packed adds, its LDS reads
+    // were regrouped into 12-byte ones (which no kernel of this library issues, gp_common.h ld1).
+    if (threadIdx.x < 144) {
+        const int c = threadIdx.x / 9, o = threadIdx.x - c * 9;
+        float f = fdiv(head_out(sm, c, o), sigma);
+        asm volatile("" : "+v"(f));
+        if (r0 + c < rows) score[(size_t)(r0 + c) * 9 + o] = fadd(f, pose_grad<EVAL_WV>(gs, c, o));
+        sm.scratch[c * 9 + o] = fmul(ld1(&sm.xin[c * 16 + o]), f);
+    }
+    if (energy != nullptr) {
+        __syncthreads();
+        if (threadIdx.x < 16 && r0 + (int)threadIdx.x < rows) {
+            float e = 0.f;
+#pragma unroll
+            for (int j = 0; j < 9; ++j) e = fadd(e, ld1(&sm.scratch[threadIdx.x * 9 + j]));
+            energy[r0 + threadIdx.x] = e;
+        }
+    }
+}
+
+extern "C" size_t gp_head_grad_floats(void) { return (size_t)16 * HID + (size_t)HID * HID + (size_t)HID * 3 * HID; }
+
+static bool grad_weights_ok(const gp_head_grad_weights* gw) { return gw && gw->pe0_wt && gw->pe2_wt && gw->h1p_wt; }
+
+extern "C" int gp_energy_score_eval(const gp_head_weights* w, const gp_head_grad_weights* gw, const float* pobj,
+                                    const float* tproj_row, float sigma, const float* x, int rows, int k,
+                                    float* score, float* energy, hipStream_t stream) {
+    GP_REQUIRE(w && grad_weights_ok(gw) && pobj && tproj_row && x && score && rows >= 0 && k >= 1 && sigma > 0.f,
+               "energy_score_eval: bad arguments");
+    if (!rows) return GP_OK;
+    hipLaunchKernelGGL(head_grad_eval_kernel, dim3((rows + 15) / 16), dim3(EVAL_WV * 64), 0, stream, *w, *gw, pobj,
+                       tproj_row, sigma, x, rows, k, score, energy);
+    return gp_check_launch("head_grad_eval_kernel");
+}
+
 // ============================================================================ PC sampler
 struct PCStep {       // one row of step_tab: {t, sigma, g, dt, sqrt_dt}
     float t, sigma, g, dt, sqrt_dt;
@@ -256,6 +318,11 @@ struct PCArgs {
     float* xs;            // (R, T, 9) or null
     int rows, kper, steps, nwg;
     float ls_coef;        // snr * sqrt(pose_dim)
+};
+// The energy-gradient step's arguments: the same, plus the transposed weights of the reverse pass. A type of its
+// own, so the other instantiations of pc_step_kernel keep their argument layout (and with it their code).
+struct PCArgsGrad : PCArgs {
+    gp_head_grad_weights gw;
 };
 
 // One update wave's part of step i-1 -> i for its 16 rows (wave g owns rows 16g .. 16g+15, four lanes per row:
@@ -423,14 +490,47 @@ __device__ __forceinline__ float pc_score_norm(const PCArgs& a, const PCStep& cu
     return t;
 }
 
+// pc_score_norm for the energy model's score, s = f / sigma + J_f^T (x / sigma) (after head_backward): the same
+// lanes, row norms and wave-order sum.
+template <int WV, typename Put>
+__device__ __forceinline__ float pc_energy_score_norm(const PCArgs& a, const PCStep& cur, HeadSmem<1, WV, 0>& sm,
+                                                      const GradSmem& gs, int r0, int wid, int lane, Put put) {
+    float wsum = 0.f;
+    for (int cg = wid; cg < 4; cg += WV) {
+        const int c = 4 * cg + (lane >> 4), o = lane & 15;
+        const int r = r0 + c;
+        float v = 0.f;
+        if (o < 9 && r < a.rows) {
+            float f = fdiv(head_out(sm, c, o), cur.sigma);
+            asm volatile("" : "+v"(f));   // keeps head_out's sum apart from pose_grad's (head_grad_eval_kernel)
+            v = fadd(f, pose_grad<WV>(gs, c, o));
+            put(c, o, v);
+        }
+        wsum += rows_sum(sqrtf(row16_sum(fmul(v, v))));
+    }
+    if (lane == 0) sm.scratch[wid] = wsum;
+    __syncthreads();
+    float t = 0.f;
+    if (wid == 0 && lane == 0) {
+#pragma unroll
+        for (int v = 0; v < WV; ++v) t += sm.scratch[v];
+    }
+    return t;
+}
+
 // Launch i in [0, steps]: finish step i-1 (if i > 0), then score at step i (if i < steps).
 // Waves 0..NT-1 run the update, one 16-row column tile each (their global loads, the draws and the
 // grad-norm reduction overlap), while the other waves make the next step's draws, stage the small
 // weights and issue their first weight-stream loads; one barrier (inside the trunk) joins them.
-template <int NT, int WV, int PL>   // PL 0: exact fp32 GEMMs, X3P: f16x3
-__global__ __launch_bounds__(WV * 64) void pc_step_kernel(PCArgs a, int i, PCStep cur, PCStep prev) {
+// GRAD: the score is the energy model's, f / sigma + J_f^T (x / sigma) (the trunk's gradient form and
+// head_backward, gp_head.h) on the transposed weights of PCArgsGrad; update waves, draws, partial slots and the
+// finalize launch are the same.
+template <int NT, int WV, int PL, bool GRAD = false>   // PL 0: exact fp32 GEMMs, X3P: f16x3
+__global__ __launch_bounds__(WV * 64) void pc_step_kernel(std::conditional_t<GRAD, PCArgsGrad, PCArgs> a, int i,
+                                                          PCStep cur, PCStep prev) {
     constexpr int ROWS = NT * 16;
     static_assert(NT < WV, "at least one wave besides the update waves");
+    static_assert(!GRAD || (NT == 1 && PL == 0), "the energy gradient runs the exact-fp32 16-candidate tile");
     __shared__ HeadSmem<NT, WV, PL> sm;
     constexpr bool SPLIT = PL != 0;
     __shared__ int obj[ROWS];
@@ -488,15 +588,26 @@ __global__ __launch_bounds__(WV * 64) void pc_step_kernel(PCArgs a, int i, PCSte
             a.zbuf[((size_t)((i & 1) * 2 + st) * a.rows + r0 + c) * 9 + e] = v;
         });
     stage_small_weights<NT, WV, 64 * NT, !SPLIT>(a.w, sm);
-    if constexpr (SPLIT)
-        head_trunk_x3<NT, WV, true>(a.w, a.pobj, a.tproj + (size_t)i * 768, obj, sm, trace_slot, hs);
-    else
-        head_trunk<NT, WV>(a.w, a.pobj, a.tproj + (size_t)i * 768, obj, sm, trace_slot);
-    PC_MARK(7);
-    const float t = pc_score_norm<NT, WV, PL>(a, cur, sm, r0, wid, lane,
-                                              [&](int c, int o, float v) { a.s[(size_t)(r0 + c) * 9 + o] = v; });
-    if (tid == 0) a.part[(size_t)(i & 1) * a.part_n + a.part_off + blockIdx.x] = t;
-    PC_MARK(8);
+    if constexpr (GRAD) {
+        __shared__ GradSmem gs;
+        head_trunk<NT, WV, false, true>(a.w, a.pobj, a.tproj + (size_t)i * 768, obj, sm, trace_slot, &gs, cur.sigma);
+        head_backward<WV>(a.gw, sm, gs, trace_slot);
+        PC_MARK(7);
+        const float t = pc_energy_score_norm<WV>(a, cur, sm, gs, r0, wid, lane,
+                                                 [&](int c, int o, float v) { a.s[(size_t)(r0 + c) * 9 + o] = v; });
+        if (tid == 0) a.part[(size_t)(i & 1) * a.part_n + a.part_off + blockIdx.x] = t;
+        PC_MARK(8);
+    } else {
+        if constexpr (SPLIT)
+            head_trunk_x3<NT, WV, true>(a.w, a.pobj, a.tproj + (size_t)i * 768, obj, sm, trace_slot, hs);
+        else
+            head_trunk<NT, WV>(a.w, a.pobj, a.tproj + (size_t)i * 768, obj, sm, trace_slot);
+        PC_MARK(7);
+        const float t = pc_score_norm<NT, WV, PL>(a, cur, sm, r0, wid, lane,
+                                                  [&](int c, int o, float v) { a.s[(size_t)(r0 + c) * 9 + o] = v; });
+        if (tid == 0) a.part[(size_t)(i & 1) * a.part_n + a.part_off + blockIdx.x] = t;
+        PC_MARK(8);
+    }
 }
 
 // Device standard normals in the PC sampler's draw layout: out[r][c] = philox_normal4(seed, stream,
@@ -571,7 +682,8 @@ static int pc_sample_impl(const gp_head_weights* w, const float* pobj, const flo
                           int steps, float* x, int rows, int k, const float* pts_center, const float* z1,
                           const float* z2, uint64_t seed, float snr, float* res, float* q, float* xs, void* workspace,
                           size_t workspace_bytes, int nt, float* part, int part_n, int part_off, int norm_rows,
-                          int row_off, gp_pc_exchange_fn exchange, void* ctx, hipStream_t stream) {
+                          int row_off, gp_pc_exchange_fn exchange, void* ctx, hipStream_t stream,
+                          const gp_head_grad_weights* gw = nullptr) {
     GP_REQUIRE(w && pobj && tproj && step_tab && x && pts_center && res && q && workspace,
                "pc_sample: null pointer");
     GP_REQUIRE(steps >= 2 && rows >= 1 && k >= 1, "pc_sample: need steps>=2, rows>=1, k>=1");
@@ -604,6 +716,7 @@ static int pc_sample_impl(const gp_head_weights* w, const float* pobj, const flo
     a.norm_rows = norm_rows;
     a.row_off = row_off;
     a.ls_coef = snr * 3.0f;  // snr * sqrt(pose_dim=9) in fp32 (0.48 rounds identically)
+    GP_REQUIRE(gw == nullptr || nt == 1, "pc_sample_energy: one 16-candidate tile per workgroup");
     GP_REQUIRE(a.part_off >= 0 && a.part_off + a.nwg <= a.part_n, "pc_sample: partials [%d, %d) outside %d entries",
                a.part_off, a.part_off + a.nwg, a.part_n);
     const dim3 grid(a.nwg);
@@ -613,7 +726,13 @@ static int pc_sample_impl(const gp_head_weights* w, const float* pobj, const flo
                                     step_tab[5 * i + 4]};
         if (i > 0) prev = PCStep{step_tab[5 * (i - 1)], step_tab[5 * (i - 1) + 1], step_tab[5 * (i - 1) + 2],
                                  step_tab[5 * (i - 1) + 3], step_tab[5 * (i - 1) + 4]};
-        if (nt == 4)
+        if (gw != nullptr) {
+            PCArgsGrad ag;
+            static_cast<PCArgs&>(ag) = a;
+            ag.gw = *gw;
+            hipLaunchKernelGGL((pc_step_kernel<1, PC_WV1, 0, true>), grid, dim3(PC_WV1 * 64), 0, stream, ag, i, cur, prev);
+        }
+        else if (nt == 4)
             hipLaunchKernelGGL((pc_step_kernel<4, PC_WV1, X3P>), grid, dim3(PC_WV1 * 64), 0, stream, a, i, cur, prev);
         else if (nt == 2)
             hipLaunchKernelGGL((pc_step_kernel<2, PC_WV1, X3P>), grid, dim3(PC_WV1 * 64), 0, stream, a, i, cur, prev);
@@ -639,6 +758,16 @@ extern "C" int gp_pc_sample(const gp_head_weights* w, const float* pobj, const f
     return pc_sample_impl(w, pobj, tproj, step_tab, steps, x, rows, k, pts_center, z1, z2, seed, snr, res, q, xs,
                           workspace, workspace_bytes, head_pick_nt(rows, w->pe2_h != nullptr), nullptr, 0, 0, rows, 0,
                           nullptr, nullptr, stream);
+}
+
+extern "C" int gp_pc_sample_energy(const gp_head_weights* w, const gp_head_grad_weights* gw, const float* pobj,
+                                   const float* tproj, const float* step_tab, int steps, float* x, int rows, int k,
+                                   const float* pts_center, const float* z1, const float* z2, uint64_t seed,
+                                   float snr, float* res, float* q, float* xs, void* workspace,
+                                   size_t workspace_bytes, hipStream_t stream) {
+    GP_REQUIRE(w != nullptr && grad_weights_ok(gw), "pc_sample_energy: null pointer");
+    return pc_sample_impl(w, pobj, tproj, step_tab, steps, x, rows, k, pts_center, z1, z2, seed, snr, res, q, xs,
+                          workspace, workspace_bytes, 1, nullptr, 0, 0, rows, 0, nullptr, nullptr, stream, gw);
 }
 
 extern "C" int gp_pc_global_partials(int rows_total, int shard_rows_max, int shards, int split) {

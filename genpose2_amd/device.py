@@ -216,6 +216,29 @@ class HeadModel:
         self.up = _Uploaded(pack.pack_heads(sd), device)
         self.set_arith(os.environ.get("GENPOSE2_HEAD_ARITH", "f16x3"))
         self._pc_ws: Optional[torch.Tensor] = None
+        self._gw = None                                    # (buffers, HeadGradWeights)
+
+    def weights_changed(self) -> None:
+        """Drop what was derived from the uploaded buffers' contents. Whoever rewrites ``up.t`` in place calls
+        this (shard.broadcast_agent does): a collective's write does not show in a tensor's version counter, so
+        nothing here could notice it."""
+        self._gw = None
+
+    @property
+    def grad_weights(self) -> "_lib.HeadGradWeights":
+        """The transposed pose-path weights of the energy gradient's reverse pass (pack.pack_heads_grad's bytes),
+        made the first time an energy-gradient call needs them: the uploaded forward fragments re-tiled on the
+        device (a copy, no arithmetic). Kept until weights_changed()."""
+        if self._gw is None:
+            src = [self.up.t[k] for k in ("pe0_w", "pe2_w", "h1p_w")]
+            bufs = {}
+            for name, t, n_out, k_in in zip(pack.HEAD_GRAD_FIELDS, src, (arch.POSE_HID, arch.POSE_HID, 3 * arch.HEAD_HID),
+                                            (16, arch.POSE_HID, arch.POSE_HID)):
+                # A fragments [T][g][q][i][j] -> W (n_out, k_in) -> fragments of W^T
+                w = t.view(n_out // 16, k_in // 16, 4, 16, 4).permute(0, 3, 1, 2, 4).reshape(n_out, k_in)
+                bufs[name] = w.t().reshape(k_in // 16, 16, n_out // 16, 4, 4).permute(0, 2, 3, 1, 4).contiguous().view(-1)
+            self._gw = (bufs, _lib.HeadGradWeights(**{k: v.data_ptr() for k, v in bufs.items()}))
+        return self._gw[1]
 
     def set_arith(self, arith: str) -> None:
         """Per-candidate GEMM arithmetic of every head kernel (PC step, score/energy eval, ODE stages):
@@ -284,10 +307,29 @@ class HeadModel:
                                       self._s()), "energy_eval")
         return out
 
+    def energy_score(self, pobj, tproj_row, sigma: float, x: torch.Tensor, k: int, want_energy: bool = False):
+        """gp_energy_score_eval: the energy model's score grad_x sum_o x_o f_o / sigma (R,9), by a reverse pass on
+        the device (exact fp32 whatever set_arith says); with want_energy also that scalar energy (R,), as
+        PoseEnergyNet.forward(return_item='score_and_energy') returns the pair."""
+        x = require_device_tensor(x, "x")
+        R = x.shape[0]
+        score = torch.empty((R, arch.POSE_DIM), dtype=torch.float32, device=self.device)
+        energy = torch.empty((R,), dtype=torch.float32, device=self.device) if want_energy else None
+        check(self.lib.gp_energy_score_eval(ctypes.byref(self.w), ctypes.byref(self.grad_weights),
+                                            ctypes.c_void_p(pobj.data_ptr()), ctypes.c_void_p(tproj_row.data_ptr()),
+                                            ctypes.c_float(sigma), ctypes.c_void_p(x.data_ptr()), R, k,
+                                            ctypes.c_void_p(score.data_ptr()), ctypes.c_void_p(_ptr(energy)),
+                                            self._s()), "energy_score_eval")
+        return (score, energy) if want_energy else score
+
     def pc_sample(self, pobj, tproj, step_tab: np.ndarray, x: torch.Tensor, k: int, pts_center: torch.Tensor,
-                  z1=None, z2=None, seed: int = 0, snr: float = arch.SNR, want_xs: bool = False, global_batch=None):
+                  z1=None, z2=None, seed: int = 0, snr: float = arch.SNR, want_xs: bool = False, global_batch=None,
+                  energy_grad: bool = False):
         """gp_pc_sample; with ``global_batch`` (shard.GlobalBatch) gp_pc_sample_global: this rank's rows of one
-        call on the whole batch (grad_norm over every shard's rows, one partials all-gather per step)."""
+        call on the whole batch (grad_norm over every shard's rows, one partials all-gather per step).
+        ``energy_grad``: gp_pc_sample_energy, the sampler driven by the energy model's score (energy_score)."""
+        if energy_grad and global_batch is not None:
+            raise NotImplementedError("the energy-gradient sampler has no global-batch mode")
         R = x.shape[0]
         T = step_tab.shape[0]
         need = int(self.lib.gp_pc_workspace_size(R))
@@ -318,6 +360,15 @@ class HeadModel:
             if ex.error is not None:
                 raise RuntimeError("pc_sample_global: partials exchange failed") from ex.error
             check(rc, "pc_sample_global")
+            return res, q, xs
+        if energy_grad:
+            check(self.lib.gp_pc_sample_energy(
+                ctypes.byref(self.w), ctypes.byref(self.grad_weights), ctypes.c_void_p(pobj.data_ptr()),
+                ctypes.c_void_p(tproj.data_ptr()), tab.ctypes.data_as(ctypes.c_void_p), T,
+                ctypes.c_void_p(x.data_ptr()), R, k, ctypes.c_void_p(pts_center.data_ptr()),
+                ctypes.c_void_p(_ptr(z1)), ctypes.c_void_p(_ptr(z2)), ctypes.c_uint64(seed), ctypes.c_float(snr),
+                ctypes.c_void_p(res.data_ptr()), ctypes.c_void_p(q.data_ptr()), ctypes.c_void_p(_ptr(xs)),
+                ctypes.c_void_p(self._pc_ws.data_ptr()), self._pc_ws.numel(), self._s()), "pc_sample_energy")
             return res, q, xs
         check(self.lib.gp_pc_sample(
             ctypes.byref(self.w), ctypes.c_void_p(pobj.data_ptr()), ctypes.c_void_p(tproj.data_ptr()),

@@ -200,6 +200,24 @@ def pack_heads(sd: weights.StateDict) -> Dict[str, np.ndarray]:
     return out
 
 
+HEAD_GRAD_FIELDS = ("pe0_wt", "pe2_wt", "h1p_wt")
+
+
+def pack_heads_grad(sd: weights.StateDict) -> Dict[str, np.ndarray]:
+    """A fragments of the transposed pose-path layers, the streamed operand of the energy gradient's reverse pass
+    (gp_head.h head_backward): pose_encoder.0^T (9 x 256, padded to one 16-row tile), pose_encoder.2^T (256 x 256)
+    and head layer 1's pose block^T (256 x 768, the three heads along K). gp_head_grad_pack writes the same bytes,
+    concatenated in this order."""
+    p = weights.head_params(sd)
+    h1_pose = p["h1_pose"].reshape(3 * arch.HEAD_HID, arch.POSE_HID)
+    out = {
+        "pe0_wt": pack_a_fragments(np.ascontiguousarray(p["pe0_w"].T), n_pad=16),
+        "pe2_wt": pack_a_fragments(np.ascontiguousarray(p["pe2_w"].T)),
+        "h1p_wt": pack_a_fragments(np.ascontiguousarray(h1_pose.T)),
+    }
+    return {k: np.ascontiguousarray(v, np.float32) for k, v in out.items()}
+
+
 SCALE_FIELDS = ("ae0_w", "ae0_b", "ae2_w", "ae2_b", "ft0_w", "ft0_b", "ft2_w", "ft2_b")
 
 

@@ -175,6 +175,8 @@ def broadcast_agent(agent, src: int = 0) -> None:
     if len(tabs) > 1:
         agent.img_encoder.set_table(tabs[1])
     agent._pc_cache = {}
+    if getattr(agent, "heads", None) is not None:
+        agent.heads.weights_changed()      # the energy gradient's transposed weights are copies of the old ones
     if dev_ is not None:
         # one-time: every copy the collective made into (or out of) the weight buffers has landed
         # before any kernel of any stream reads them (gloo moves CUDA tensors on its own streams)

@@ -240,6 +240,26 @@ int gp_energy_eval(const gp_head_weights *w, const float *pobj, const float *tpr
                    float sigma, const float *pose, int rows, int k, float *energy,
                    hipStream_t stream);
 
+/* Energy model as a score model (PoseEnergyNet.forward(return_item='score'), energynet.py:211-233):
+ * score = grad_x E with E = sum_o x_o f_o(x) / sigma (IP / score / identical, decoupled_rt=False), i.e.
+ * score_o = f_o / sigma + (J_f^T c)_o with the cotangent c = x / sigma: one reverse pass through the
+ * pose-dependent layers on the transposed weights below, with the forward pass's ReLU masks (relu' = 0 at 0).
+ * Forward and reverse GEMMs are exact fp32 MFMA whatever gp_head_weights' f16x3 fields hold. */
+typedef struct {
+    const float *pe0_wt; /* packed A fragments of pose_encoder.0^T, 16 x 256 (rows 9..15 zero) */
+    const float *pe2_wt; /* ... of pose_encoder.2^T, 256 x 256 */
+    const float *h1p_wt; /* ... of (head layer 1 pose block)^T, 256 x 768 */
+} gp_head_grad_weights;
+size_t gp_head_grad_floats(void); /* 16*256 + 256*256 + 256*768 */
+/* HOST: row-major pe0_w (256,9), pe2_w (256,256), h1_pose (768,256: the three heads' pose columns, head-major)
+ * -> out (gp_head_grad_floats()) = pe0_wt | pe2_wt | h1p_wt; byte-identical to pack.pack_heads_grad */
+int gp_head_grad_pack(const float *pe0_w, const float *pe2_w, const float *h1_pose, float *out);
+/* score (R,9) = grad_x of sum_o x_o f_o / sigma; energy: NULL or (R) that scalar (return_item
+ * 'score_and_energy'). Rows r -> object r / k; a row's result does not depend on the rows evaluated with it. */
+int gp_energy_score_eval(const gp_head_weights *w, const gp_head_grad_weights *gw, const float *pobj,
+                         const float *tproj_row, float sigma, const float *x, int rows, int k,
+                         float *score, float *energy, hipStream_t stream);
+
 /* ===================================================================== PC sampler
  * cond_pc_sampler (samplers.py:113-177) for R = b*k rows over T steps, fused per step:
  * [finish step i-1: Langevin corrector with the batch-mean score norm, renormalise,
@@ -258,6 +278,13 @@ int gp_pc_sample(const gp_head_weights *w, const float *pobj, const float *tproj
                  const float *pts_center, const float *z1, const float *z2, uint64_t seed,
                  float snr, float *res, float *q, float *xs, void *workspace,
                  size_t workspace_bytes, hipStream_t stream);
+/* gp_pc_sample with the energy model's score (gp_energy_score_eval's, sigma without the + 1e-7) in place of
+ * the ScoreNet's: same arguments, workspace, noise streams and outputs; 16 candidates per workgroup. */
+int gp_pc_sample_energy(const gp_head_weights *w, const gp_head_grad_weights *gw, const float *pobj,
+                        const float *tproj, const float *step_tab, int steps, float *x, int rows, int k,
+                        const float *pts_center, const float *z1, const float *z2, uint64_t seed,
+                        float snr, float *res, float *q, float *xs, void *workspace,
+                        size_t workspace_bytes, hipStream_t stream);
 
 /* Global-batch PC sampling over shards (SURVEY 8e's optional mode; replaces nothing in the reference,
  * whose single cond_pc_sampler call (samplers.py:113-177) couples every row of the batch through the
