@@ -25,7 +25,7 @@ class GenPoseHipError(RuntimeError):
 class HeadWeights(ctypes.Structure):
     _fields_ = [(n, c_void_p) for n in ("pe0_w", "pe0_b", "pe2_w", "pe2_b", "h1p_w", "h2_w", "h2_b",
                                        "h1pts_t", "h1_b", "gfp_w", "te_w_t", "te_b", "h1t_t", "pe2_h", "h1p_h",
-                                       "hsc")]
+                                       "hsc", "pe2_q", "h1p_q")] + [("q8_flags", c_size_t)]
 
 
 class HeadGradWeights(ctypes.Structure):

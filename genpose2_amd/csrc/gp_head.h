@@ -38,13 +38,14 @@ __device__ __forceinline__ int tid_x() {
 
 // ============================================================================ shared head trunk
 // NT = column tiles (16 candidates each) per workgroup. PL = 0: the exact-fp32 trunk's activations
-// (fp32, accumulator-native); PL = 3: the f16x3 trunk's (three f16 planes per value, 6 B).
+// (fp32, accumulator-native); PL = 3: the f16x3 trunk's (three f16 planes per value, 6 B); PL = 4 (X3Q): the
+// hybrid trunk's (two f16 planes and three e4m3 planes per value, 7 B: act_plane / act_q8 below).
 template <int NT, int WV, int PL = 0>
 struct HeadSmem {
     // 64-candidate tiles (NT = 4) alias pose_encoder.2's output onto pose_encoder.0's (written after
     // a barrier that retires every read of act1), so one workgroup still fits the 160 KiB of a CU
     static constexpr bool kAliasAct = NT >= 4;
-    static constexpr int kAct = PL ? (HID / 32) * NT * PL * 64 : KG_HID * NT * 64;   // 16-byte entries
+    static constexpr int kAct = PL == 4 ? (HID / 32) * NT * 224 : (PL ? (HID / 32) * NT * PL * 64 : KG_HID * NT * 64);   // 16-byte entries
     float xin[NT * 16 * 16];           // input poses, [col][16] (9 used)
     f32x4 act1[kAct];                  // pose_encoder.0 output: [g][ct][lane] (fp32) / [chunk][ct][plane][lane]
     f32x4 act2[kAliasAct ? 4 : kAct];  // pose_encoder.2 output (act1 when aliased)
@@ -631,6 +632,68 @@ __device__ __forceinline__ float xin_row_absmax(f32x4 b) {
 #endif
 constexpr int X3P = 3;           // planes per operand
 
+// ---- hybrid form (PL = X3Q): the three products of plane order 2 on block-scaled FP8 MFMA
+// Of the six products, hi*hi, hi*mid and mid*hi carry everything down to 2^-22 of the leading product and stay
+// on f16; w_hi*a_lo, w_mid*a_mid and w_lo*a_hi are each <= 2^-22 of it, so e4m3's four significant bits per
+// operand leave their error near 2^-26 per product (scripts/x3q_error_model.py: the score error stays below
+// exact fp32's). They run on v_mfma_scale_f32_16x16x128_f8f6f4, one instruction per product and 128-deep group
+// (32 cycles against the 4 x 16 of the f16 form), into `cor`: per 128-deep group and tile 12 f16 + 3 FP8
+// MFMAs, 288 cycles against 384.
+// An e4m3 plane is the f16 plane times a constant power of two that brings the plane's bound to 2^7..2^8
+// (hi < 2^15 -> x 2^-7, |mid| <= 2^3 -> x 2^4, |lo| <= 2^-9 -> x 2^16; e4m3's largest value is 448), converted
+// with v_cvt_pk_fp8_f32 (round to nearest even, subnormals kept). The instruction's E8M0 block scales, constants,
+// undo the two planes' constants, so the products enter `cor` in the scaled domain of the f16 ones.
+// Product k of a group is issued with chunk 4g + k of the f16 stream (k < 3), its A planes riding in that chunk's
+// ring slot. Lane (q, i) of an operand holds 32 bytes per group: byte 8 cc + j is element j of the lane's f16
+// fragment of chunk 4g + cc (the same k in A and B, which is all the sum needs).
+// LDS, per activation buffer (16-byte entries): f16 planes [chunk][ct][hi, mid][lane], then the e4m3 planes
+// [group][ct][product][half][lane] (product k's B operand: a_lo8, a_mid8, a_hi8).
+// Weights: pack.pack_q8_fragments, [T][group][product][half][lane] (w_hi8, w_mid8, w_lo8).
+constexpr int X3Q = 4;           // HeadSmem / trunk PL of the hybrid form
+typedef int i32x8 __attribute__((ext_vector_type(8)));
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+constexpr int Q8_EXP_HI = -7, Q8_EXP_MID = 4, Q8_EXP_LO = 16;   // e4m3 plane = f16 plane x 2^this
+template <int PL>
+constexpr int act_f16_planes() { return PL == X3Q ? 2 : X3P; }
+// 16-byte entry of f16 plane p of (chunk, column tile), lane 0
+template <int PL, int NT>
+__device__ __forceinline__ constexpr int act_plane(int chunk, int ct, int p) {
+    return ((chunk * NT + ct) * act_f16_planes<PL>() + p) * 64;
+}
+// 16-byte entry of half h of product k's e4m3 B operand of (group, column tile), lane 0
+template <int NT>
+__device__ __forceinline__ constexpr int act_q8(int group, int ct, int k, int h) {
+    return KC_HID * NT * 2 * 64 + (((group * NT + ct) * 3 + k) * 2 + h) * 64;
+}
+// product k of w (A) and activation (B) e4m3 planes, c += A . B x 2^-(the two planes' exponents)
+template <int K>
+__device__ __forceinline__ f32x4 mfma_q8(f16x8 a0, f16x8 a1, f16x8 b0, f16x8 b1, f32x4 c) {
+    using u4 = __attribute__((ext_vector_type(4))) int;
+    const u4 x0 = __builtin_bit_cast(u4, a0), x1 = __builtin_bit_cast(u4, a1);
+    const u4 y0 = __builtin_bit_cast(u4, b0), y1 = __builtin_bit_cast(u4, b1);
+    const i32x8 a = {x0[0], x0[1], x0[2], x0[3], x1[0], x1[1], x1[2], x1[3]};
+    const i32x8 b = {y0[0], y0[1], y0[2], y0[3], y1[0], y1[1], y1[2], y1[3]};
+    // weight planes hi8, mid8, lo8 meet activation planes lo8, mid8, hi8
+    constexpr int ea = K == 0 ? Q8_EXP_HI : (K == 1 ? Q8_EXP_MID : Q8_EXP_LO);
+    constexpr int eb = K == 0 ? Q8_EXP_LO : (K == 1 ? Q8_EXP_MID : Q8_EXP_HI);
+    return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, b, c, 0, 0, 0, 127 - ea, 0, 127 - eb);
+}
+// the 8 e4m3 bytes of one f16 fragment times 2^e (element j -> byte j)
+__device__ __forceinline__ u32x2 q8_of(f16x8 p, float s) {
+    int lo = 0, hi = 0;
+    lo = __builtin_amdgcn_cvt_pk_fp8_f32((float)p[0] * s, (float)p[1] * s, lo, false);
+    lo = __builtin_amdgcn_cvt_pk_fp8_f32((float)p[2] * s, (float)p[3] * s, lo, true);
+    hi = __builtin_amdgcn_cvt_pk_fp8_f32((float)p[4] * s, (float)p[5] * s, hi, false);
+    hi = __builtin_amdgcn_cvt_pk_fp8_f32((float)p[6] * s, (float)p[7] * s, hi, true);
+    return u32x2{(unsigned)lo, (unsigned)hi};
+}
+// One (chunk, column tile)'s planes as the epilogues hold them between the split and the LDS write
+template <int PL>
+struct ActPlanes {
+    f16x8 h[act_f16_planes<PL>()];
+    u32x2 q[PL == X3Q ? 3 : 1];   // X3Q: the e4m3 bytes of products 0..2's B operands (a_lo8, a_mid8, a_hi8)
+};
+
 // x = h + m + l exactly (x finite, |x| < 65504; f16 subnormals aside)
 __device__ __forceinline__ void split3(float x, _Float16& h, _Float16& m, _Float16& l) {
 #pragma clang fp contract(off)
@@ -653,6 +716,33 @@ __device__ __forceinline__ void split3_pair(f32x4 u, f32x4 v, float s, f16x8 (&p
         p[2][j] = l;
     }
 }
+// split3_pair into the planes the PL form keeps: X3P the three f16 planes; X3Q hi, mid and the e4m3 planes
+template <int PL>
+__device__ __forceinline__ void split_act(f32x4 u, f32x4 v, float s, ActPlanes<PL>& a) {
+    f16x8 p[X3P];
+    split3_pair(u, v, s, p);
+    a.h[0] = p[0];
+    a.h[1] = p[1];
+    if constexpr (PL == X3Q) {
+        a.q[0] = q8_of(p[2], exp2i(Q8_EXP_LO));
+        a.q[1] = q8_of(p[1], exp2i(Q8_EXP_MID));
+        a.q[2] = q8_of(p[0], exp2i(Q8_EXP_HI));
+    } else {
+        a.h[2] = p[2];
+    }
+}
+// ... written to the activation buffer `act` as (chunk, column tile ct)'s B planes
+template <int PL, int NT>
+__device__ __forceinline__ void store_act(f16x8* act, int chunk, int ct, int lane, const ActPlanes<PL>& a) {
+#pragma unroll
+    for (int p = 0; p < act_f16_planes<PL>(); ++p) act[act_plane<PL, NT>(chunk, ct, p) + lane] = a.h[p];
+    if constexpr (PL == X3Q) {
+        const int cc = chunk & 3;
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+            reinterpret_cast<u32x2*>(act + act_q8<NT>(chunk >> 2, ct, k, cc >> 1) + lane)[cc & 1] = a.q[k];
+    }
+}
 
 // One pipelined step of a 256-deep f16x3 layer: step G issues the loads of chunk G (tile T[t]'s three
 // weight planes, 3 KiB per tile: pack_h16_fragments' [T][c][plane][lane]) and computes chunk G - D from
@@ -661,22 +751,63 @@ __device__ __forceinline__ void split3_pair(f32x4 u, f32x4 v, float s, f16x8 (&p
 // run (X3_BPIPE; sched barriers keep the compiler from sinking the reads to their first use, where
 // each became an lgkmcnt(0) stall). Steps 0..D-1 only prime the ring (no B or accumulator access), so
 // they can run before a barrier or under another phase.
-template <int G, int GEND, int TT, int NT, int D>
-__device__ __forceinline__ void stream_x3_rec(__amdgpu_buffer_rsrc_t W, const int (&T)[TT], const f16x8* __restrict__ B,
-                                              int lane, int voff, f16x8 (&ring)[D + 1][TT][X3P],
-                                              f32x4 (&acc)[TT][NT], f32x4 (&cor)[TT][NT], f16x8 (&bc)[X3P]) {
+// PL = X3Q (hybrid): a ring slot holds the chunk's hi and mid planes and, for a chunk that carries a product
+// (G % 4 < 3), the two halves of that product's e4m3 A operand from WQ; cor += product k, mid*hi, hi*mid.
+template <int PL>
+constexpr int ring_planes() { return PL == X3Q ? 4 : X3P; }
+// The B planes of (chunk GG, column tile ct): the f16 planes, then (X3Q, a chunk with a product) its e4m3 halves
+template <int PL, int NT>
+__device__ __forceinline__ void load_b_planes(const f16x8* __restrict__ B, int GG, int ct, int lane,
+                                              f16x8 (&b)[ring_planes<PL>()]) {
+#pragma unroll
+    for (int p = 0; p < act_f16_planes<PL>(); ++p) b[p] = B[act_plane<PL, NT>(GG, ct, p) + lane];
+    if constexpr (PL == X3Q) {
+        if ((GG & 3) < 3) {
+            b[2] = B[act_q8<NT>(GG >> 2, ct, GG & 3, 0) + lane];
+            b[3] = B[act_q8<NT>(GG >> 2, ct, GG & 3, 1) + lane];
+        }
+    }
+}
+// One tile's correction products of chunk GG (KQ = GG % 4): X3P smallest first; X3Q the 8-pass FP8 instruction
+// last, so that the MFMA issued after it (another tile's or the main product) does not wait for its result
+template <int PL, int KQ>
+__device__ __forceinline__ f32x4 cross_products(const f16x8 (&w)[ring_planes<PL>()], const f16x8 (&b)[ring_planes<PL>()],
+                                                f32x4 c) {
+    if constexpr (PL != X3Q) {
+        c = mfma_h(w[2], b[0], c);
+        c = mfma_h(w[0], b[2], c);
+        c = mfma_h(w[1], b[1], c);
+    }
+    c = mfma_h(w[1], b[0], c);
+    c = mfma_h(w[0], b[1], c);
+    if constexpr (PL == X3Q && KQ < 3) c = mfma_q8<KQ < 3 ? KQ : 0>(w[2], w[3], b[2], b[3], c);
+    return c;
+}
+template <int PL, int G, int GEND, int TT, int NT, int D>
+__device__ __forceinline__ void stream_x3_rec(__amdgpu_buffer_rsrc_t W, __amdgpu_buffer_rsrc_t WQ, const int (&T)[TT],
+                                              const f16x8* __restrict__ B, int lane, int voff,
+                                              f16x8 (&ring)[D + 1][TT][ring_planes<PL>()], f32x4 (&acc)[TT][NT],
+                                              f32x4 (&cor)[TT][NT], f16x8 (&bc)[ring_planes<PL>()]) {
+    constexpr int RP = ring_planes<PL>();
     if constexpr (G < GEND) {
         if constexpr (G < KC_HID && ((X3_DIAG & 2) == 0 || G < D + 1)) {
 #pragma unroll
-            for (int t = 0; t < TT; ++t)
+            for (int t = 0; t < TT; ++t) {
 #pragma unroll
-                for (int p = 0; p < X3P; ++p)
+                for (int p = 0; p < act_f16_planes<PL>(); ++p)
                     ring[G % (D + 1)][t][p] =
                         __builtin_bit_cast(f16x8, ldbuf4(W, voff, ((T[t] * KC_HID + G) * X3P + p) * 1024));
+                if constexpr (PL == X3Q && (G & 3) < 3) {
+#pragma unroll
+                    for (int h = 0; h < 2; ++h)
+                        ring[G % (D + 1)][t][2 + h] = __builtin_bit_cast(
+                            f16x8, ldbuf4(WQ, voff, (((T[t] * (KC_HID / 4) + G / 4) * 3 + (G & 3)) * 2 + h) * 1024));
+                }
+            }
         }
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (G >= D) {
-            constexpr int GG = G - D, S = GG % (D + 1);
+            constexpr int GG = G - D, S = GG % (D + 1), KQ = GG & 3;
 #if X3_PRIO
             // the two waves of a SIMD (w, w + 4) take turns at issue priority chunk by chunk, so neither runs
             // a whole stream ahead and leaves the other to finish it alone (tuning variant)
@@ -688,92 +819,73 @@ __device__ __forceinline__ void stream_x3_rec(__amdgpu_buffer_rsrc_t W, const in
 #if X3_BPIPE
             // B planes one column tile ahead: column tile ct + 1's (or the next chunk's first) reads are in
             // flight during column tile ct's MFMAs
-            if constexpr (GG == 0) {
-#pragma unroll
-                for (int p = 0; p < X3P; ++p) bc[p] = B[p * 64 + lane];
-            }
+            if constexpr (GG == 0) load_b_planes<PL, NT>(B, 0, 0, lane, bc);
 #pragma unroll
             for (int ct = 0; ct < NT; ++ct) {
-                f16x8 bn[X3P];
-                const int nx = ct + 1 < NT ? (GG * NT + ct + 1) : ((GG + 1) * NT);
-                if ((X3_DIAG & 1) == 0 && (ct + 1 < NT || GG + 1 < KC_HID)) {
-#pragma unroll
-                    for (int p = 0; p < X3P; ++p) bn[p] = B[(nx * X3P + p) * 64 + lane];
-                }
+                f16x8 bn[RP];
+                const int ng = ct + 1 < NT ? GG : GG + 1, nc = ct + 1 < NT ? ct + 1 : 0;
+                if ((X3_DIAG & 1) == 0 && (ct + 1 < NT || GG + 1 < KC_HID)) load_b_planes<PL, NT>(B, ng, nc, lane, bn);
 #if X3_DIAG & 1
 #pragma unroll
-                for (int p = 0; p < X3P; ++p) {   // distinct operands per tile, so the MFMAs stay distinct
+                for (int p = 0; p < RP; ++p) {   // distinct operands per tile, so the MFMAs stay distinct
                     using u4 = __attribute__((ext_vector_type(4))) unsigned;
-                    bn[p] = __builtin_bit_cast(f16x8, __builtin_bit_cast(u4, bc[p]) ^ (unsigned)(nx + 1));
+                    bn[p] = __builtin_bit_cast(f16x8, __builtin_bit_cast(u4, bc[p]) ^ (unsigned)(ng * NT + nc + 1));
                 }
 #endif
                 __builtin_amdgcn_sched_barrier(0);   // the reads stay ahead of this column tile's MFMAs
-                const f16x8 b0 = bc[0], b1 = bc[1], b2 = bc[2];
+                f16x8 b[RP];
+#pragma unroll
+                for (int p = 0; p < RP; ++p) b[p] = bc[p];
 #if X3_CHAIN
-                // each tile's five correction products back to back on one accumulator, then the main
+                // each tile's correction products back to back on one accumulator, then the main
                 // products (the issue rate itself does not depend on the order, scripts/mfma_chain_probe.hip;
                 // this order measured 3 % faster at two passes, even at one)
 #pragma unroll
                 for (int t = 0; t < TT; ++t) {
-                    f32x4 c = cor[t][ct];
-                    c = mfma_h(ring[S][t][2], b0, c);
-                    c = mfma_h(ring[S][t][0], b2, c);
-                    c = mfma_h(ring[S][t][1], b1, c);
-                    c = mfma_h(ring[S][t][1], b0, c);
-                    c = mfma_h(ring[S][t][0], b1, c);
-                    cor[t][ct] = c;
+                    cor[t][ct] = cross_products<PL, KQ>(ring[S][t], b, cor[t][ct]);
                     __builtin_amdgcn_sched_barrier(0);
                 }
 #pragma unroll
-                for (int t = 0; t < TT; ++t) acc[t][ct] = mfma_h(ring[S][t][0], b0, acc[t][ct]);
+                for (int t = 0; t < TT; ++t) acc[t][ct] = mfma_h(ring[S][t][0], b[0], acc[t][ct]);
 #else
 #pragma unroll
                 for (int t = 0; t < TT; ++t) {
-                    f32x4 c = cor[t][ct];
-                    c = mfma_h(ring[S][t][2], b0, c);
-                    c = mfma_h(ring[S][t][0], b2, c);
-                    c = mfma_h(ring[S][t][1], b1, c);
-                    c = mfma_h(ring[S][t][1], b0, c);
-                    c = mfma_h(ring[S][t][0], b1, c);
-                    cor[t][ct] = c;
-                    acc[t][ct] = mfma_h(ring[S][t][0], b0, acc[t][ct]);
+                    cor[t][ct] = cross_products<PL, KQ>(ring[S][t], b, cor[t][ct]);
+                    acc[t][ct] = mfma_h(ring[S][t][0], b[0], acc[t][ct]);
                 }
 #endif
                 __builtin_amdgcn_sched_barrier(0);
                 if (ct + 1 < NT || GG + 1 < KC_HID) {
 #pragma unroll
-                    for (int p = 0; p < X3P; ++p) bc[p] = bn[p];
+                    for (int p = 0; p < RP; ++p) bc[p] = bn[p];
                 }
             }
 #else
 #pragma unroll
             for (int ct = 0; ct < NT; ++ct) {
-                const f16x8 b0 = B[((GG * NT + ct) * X3P + 0) * 64 + lane];
-                const f16x8 b1 = B[((GG * NT + ct) * X3P + 1) * 64 + lane];
-                const f16x8 b2 = B[((GG * NT + ct) * X3P + 2) * 64 + lane];
+                f16x8 b[RP];
+                load_b_planes<PL, NT>(B, GG, ct, lane, b);
 #pragma unroll
                 for (int t = 0; t < TT; ++t) {
-                    f32x4 c = cor[t][ct];
-                    c = mfma_h(ring[S][t][2], b0, c);
-                    c = mfma_h(ring[S][t][0], b2, c);
-                    c = mfma_h(ring[S][t][1], b1, c);
-                    c = mfma_h(ring[S][t][1], b0, c);
-                    c = mfma_h(ring[S][t][0], b1, c);
-                    cor[t][ct] = c;
-                    acc[t][ct] = mfma_h(ring[S][t][0], b0, acc[t][ct]);
+                    cor[t][ct] = cross_products<PL, KQ>(ring[S][t], b, cor[t][ct]);
+                    acc[t][ct] = mfma_h(ring[S][t][0], b[0], acc[t][ct]);
                 }
             }
 #endif
         }
-        stream_x3_rec<G + 1, GEND, TT, NT, D>(W, T, B, lane, voff, ring, acc, cor, bc);
+        stream_x3_rec<PL, G + 1, GEND, TT, NT, D>(W, WQ, T, B, lane, voff, ring, acc, cor, bc);
     }
 }
-template <int G, int GEND, int TT, int NT, int D>
-__device__ __forceinline__ void stream_x3_step(__amdgpu_buffer_rsrc_t W, const int (&T)[TT], const f16x8* __restrict__ B,
-                                               int lane, int voff, f16x8 (&ring)[D + 1][TT][X3P],
+// The weight planes a trunk streams: the f16 planes and, for the hybrid form, the e4m3 ones (W again otherwise)
+struct X3Weights {
+    __amdgpu_buffer_rsrc_t W, WQ;
+};
+template <int PL, int G, int GEND, int TT, int NT, int D>
+__device__ __forceinline__ void stream_x3_step(const X3Weights& w, const int (&T)[TT], const f16x8* __restrict__ B,
+                                               int lane, int voff, f16x8 (&ring)[D + 1][TT][ring_planes<PL>()],
                                                f32x4 (&acc)[TT][NT], f32x4 (&cor)[TT][NT]) {
-    f16x8 bc[X3P];   // X3_BPIPE: the B planes of the next column tile, carried from step to step
-    stream_x3_rec<G, GEND, TT, NT, D>(W, T, B, lane, voff, ring, acc, cor, bc);
+    f16x8 bc[ring_planes<PL>()];   // X3_BPIPE: the B planes of the next column tile, carried from step to step
+    stream_x3_rec<PL, G, GEND, TT, NT, D>(w.W, w.WQ, T, B, lane, voff, ring, acc, cor, bc);
 }
 
 // The fp32 init rows of head layer 1 (hoisted pts + t blocks: pobj of each column's object, tproj) for this
@@ -801,13 +913,13 @@ __device__ __forceinline__ void head_x3_init_load(__amdgpu_buffer_rsrc_t RP, __a
 // PRE: the caller wrote every column's ColScales to sm.cscl before the trunk's first barrier (the PC
 // step's update waves, which hold the rows), so the trunk reads them instead of recomputing them in
 // every wave.
-template <int H, int NT, int WV, int TPW, int DH, bool JVP = false>
-__device__ __forceinline__ void head_x3_head(__amdgpu_buffer_rsrc_t WH, const f16x8* __restrict__ act2h,
+template <int H, int NT, int WV, int TPW, int DH, bool JVP = false, int PL = X3P>
+__device__ __forceinline__ void head_x3_head(const X3Weights& WH, const f16x8* __restrict__ act2h,
                                              __amdgpu_buffer_rsrc_t RP, __amdgpu_buffer_rsrc_t RT, const int (&vo)[NT],
-                                             HeadSmem<NT, WV, X3P>& sm, const float (&uh)[NT], const float (&sh)[NT],
-                                             int wid, int lane, f16x8 (&ringh)[DH + 1][TPW][X3P],
+                                             HeadSmem<NT, WV, PL>& sm, const float (&uh)[NT], const float (&sh)[NT],
+                                             int wid, int lane, f16x8 (&ringh)[DH + 1][TPW][ring_planes<PL>()],
                                              f32x4 (&tpv)[TPW], f32x4 (&pov)[TPW][JVP ? NT / 2 : NT],
-                                             float (&pv)[HeadSmem<NT, WV, X3P>::kRedV]) {
+                                             float (&pv)[HeadSmem<NT, WV, PL>::kRedV]) {
     constexpr int NP = JVP ? NT / 2 : NT;
     const int q = lane >> 4, n = lane & 15;
     const int voff = lane * 16;
@@ -827,12 +939,12 @@ __device__ __forceinline__ void head_x3_head(__amdgpu_buffer_rsrc_t WH, const f1
             }
             cor[t][ct] = f32x4{0.f, 0.f, 0.f, 0.f};
         }
-    stream_x3_step<DH, KC_HID + DH, TPW, NT, DH>(WH, TH, act2h, lane, voff, ringh, acc, cor);
+    stream_x3_step<PL, DH, KC_HID + DH, TPW, NT, DH>(WH, TH, act2h, lane, voff, ringh, acc, cor);
     if constexpr (H < 2) {   // the next head's first chunks and init rows, in flight across this epilogue
         int TN[TPW];
 #pragma unroll
         for (int t = 0; t < TPW; ++t) TN[t] = TH[t] + 16;
-        stream_x3_step<0, DH, TPW, NT, DH>(WH, TN, act2h, lane, voff, ringh, acc, cor);
+        stream_x3_step<PL, 0, DH, TPW, NT, DH>(WH, TN, act2h, lane, voff, ringh, acc, cor);
         head_x3_init_load<H + 1, NT, TPW, NP>(RP, RT, vo, wid, lane, tpv, pov);
     }
     // nothing below is scheduled into the MFMA stream above: interleaved there, the row swaps of the
@@ -891,24 +1003,31 @@ __device__ __forceinline__ void head_x3_head(__amdgpu_buffer_rsrc_t WH, const f1
     __builtin_amdgcn_sched_barrier(0);
 }
 
-template <int NT, int WV, bool PRE = false, bool JVP = false>
+// PL (taken from sm): X3P the six f16 products; X3Q the hybrid form (w.pe2_q / w.h1p_q must be given)
+template <int NT, int WV, bool PRE = false, bool JVP = false, int PL = X3P>
 __device__ __forceinline__ void head_trunk_x3(const gp_head_weights& w, const float* __restrict__ pobj,
                                               const float* __restrict__ tproj, const int* obj_of_col,
-                                              HeadSmem<NT, WV, X3P>& sm, int trace_slot, const SplitScalars hs) {
+                                              HeadSmem<NT, WV, PL>& sm, int trace_slot, const SplitScalars hs) {
+    static_assert(PL == X3P || (PL == X3Q && !JVP), "the hybrid form has no tangent tiles");
     constexpr int TPW = 16 / WV;   // output tiles per wave and 256-wide layer; tiles (2c, 2c+1) form chunk c
     static_assert(TPW % 2 == 0, "the f16x3 trunk pairs a wave's output tiles into 32-deep chunks");
     static_assert(TPW <= 4, "SplitScalars carries at most four pose_encoder.0 tiles per wave");
     constexpr int CPW = TPW / 2;
     constexpr int NP = JVP ? NT / 2 : NT;   // primal column tiles (tangent tile ct pairs with ct - NP)
     static_assert(!JVP || NT % 2 == 0, "a JVP trunk pairs every primal tile with a tangent tile");
-    using SM = HeadSmem<NT, WV, X3P>;
+    using SM = HeadSmem<NT, WV, PL>;
     const int tid = tid_x();
     const int lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int q = lane >> 4, n = lane & 15;
     const int voff = lane * 16;
-    const __amdgpu_buffer_rsrc_t W2 = make_rsrc(w.pe2_h, HID * HID * 2 * X3P);
-    const __amdgpu_buffer_rsrc_t WH = make_rsrc(w.h1p_h, 3 * HID * HID * 2 * X3P);
+    X3Weights W2, WH;
+    W2.W = W2.WQ = make_rsrc(w.pe2_h, HID * HID * 2 * X3P);
+    WH.W = WH.WQ = make_rsrc(w.h1p_h, 3 * HID * HID * 2 * X3P);
+    if constexpr (PL == X3Q) {
+        W2.WQ = make_rsrc(w.pe2_q, HID * HID * 3);
+        WH.WQ = make_rsrc(w.h1p_q, 3 * HID * HID * 3);
+    }
     f16x8* act1h = reinterpret_cast<f16x8*>(sm.act1);
     f16x8* act2h = reinterpret_cast<f16x8*>(SM::kAliasAct ? sm.act1 : sm.act2);
     constexpr int D2 = X3_D2, DH = X3_DH;
@@ -920,8 +1039,8 @@ __device__ __forceinline__ void head_trunk_x3(const gp_head_weights& w, const fl
     for (int t = 0; t < TPW; ++t)
 #pragma unroll
         for (int ct = 0; ct < NT; ++ct) acc2[t][ct] = cor2[t][ct] = f32x4{0.f, 0.f, 0.f, 0.f};
-    f16x8 ring2[D2 + 1][TPW][X3P];
-    stream_x3_step<0, D2, TPW, NT, D2>(W2, T2, act1h, lane, voff, ring2, acc2, cor2);
+    f16x8 ring2[D2 + 1][TPW][ring_planes<PL>()];
+    stream_x3_step<PL, 0, D2, TPW, NT, D2>(W2, T2, act1h, lane, voff, ring2, acc2, cor2);
     __syncthreads();
     PC_MARK(1);
     // ---- per-candidate exponents: bound1 >= |pose_encoder.0 out|, bound2 >= |pose_encoder.2 out|
@@ -964,24 +1083,24 @@ __device__ __forceinline__ void head_trunk_x3(const gp_head_weights& w, const fl
 #pragma unroll
                 for (int p = 0; p < X3P; ++p) act1h[(((Ta >> 1) * NT + ct + dt) * X3P + p) * 64 + lane] = pl[p];
             } else {
-                split3_pair(relu4(mfma_kgroup(a0, bf[ct], z) + bias0), relu4(mfma_kgroup(a1, bf[ct], z) + bias1), s1[ct], pl);
-#pragma unroll
-                for (int p = 0; p < X3P; ++p) act1h[(((Ta >> 1) * NT + ct) * X3P + p) * 64 + lane] = pl[p];
+                ActPlanes<PL> ap;
+                split_act<PL>(relu4(mfma_kgroup(a0, bf[ct], z) + bias0), relu4(mfma_kgroup(a1, bf[ct], z) + bias1), s1[ct], ap);
+                store_act<PL, NT>(act1h, Ta >> 1, ct, lane, ap);
             }
         }
     }
     __syncthreads();
     PC_MARK(2);
     // ---- pose_encoder.2 (256 -> 256)
-    stream_x3_step<D2, KC_HID + D2, TPW, NT, D2>(W2, T2, act1h, lane, voff, ring2, acc2, cor2);
+    stream_x3_step<PL, D2, KC_HID + D2, TPW, NT, D2>(W2, T2, act1h, lane, voff, ring2, acc2, cor2);
     PC_MARK(3);
     // head layer 1's first chunks and init rows (head 0), in flight across the pose_encoder.2 epilogue
-    f16x8 ringh[DH + 1][TPW][X3P];
+    f16x8 ringh[DH + 1][TPW][ring_planes<PL>()];
     {
         int TH0[TPW];
 #pragma unroll
         for (int t = 0; t < TPW; ++t) TH0[t] = wid * TPW + t;
-        stream_x3_step<0, DH, TPW, NT, DH>(WH, TH0, act2h, lane, voff, ringh, acc2, cor2);
+        stream_x3_step<PL, 0, DH, TPW, NT, DH>(WH, TH0, act2h, lane, voff, ringh, acc2, cor2);
     }
     const __amdgpu_buffer_rsrc_t RP = make_rsrc(pobj, 0x7ffffff0u), RT = make_rsrc(tproj, 3 * HID * 4);
     int vo[NT];
@@ -992,7 +1111,7 @@ __device__ __forceinline__ void head_trunk_x3(const gp_head_weights& w, const fl
 #if X3_EPI_EARLY
     // the epilogue's planes are made before the alias barrier (a wave that finished its stream early does
     // this VALU work while it waits for the last one) and only written after it
-    f16x8 pls[CPW][NT][X3P];
+    ActPlanes<PL> pls[CPW][NT];
 #pragma unroll
     for (int c = 0; c < CPW; ++c) {
         const int Ta = T2[2 * c];
@@ -1003,13 +1122,13 @@ __device__ __forceinline__ void head_trunk_x3(const gp_head_weights& w, const fl
                 constexpr int dt = JVP ? NP : 0;
                 const f32x4 pre0 = (acc2[2 * c][ct] + cor2[2 * c][ct]) * u2[ct] + bias0;
                 const f32x4 pre1 = (acc2[2 * c + 1][ct] + cor2[2 * c + 1][ct]) * u2[ct] + bias1;
-                split3_pair(relu4(pre0), relu4(pre1), s2[ct], pls[c][ct]);
+                split3_pair(relu4(pre0), relu4(pre1), s2[ct], pls[c][ct].h);
                 split3_pair(mask4((acc2[2 * c][ct + dt] + cor2[2 * c][ct + dt]) * u2[ct + dt], pre0),
                             mask4((acc2[2 * c + 1][ct + dt] + cor2[2 * c + 1][ct + dt]) * u2[ct + dt], pre1),
-                            s2[ct + dt], pls[c][ct + dt]);
+                            s2[ct + dt], pls[c][ct + dt].h);
             } else {
-                split3_pair(relu4((acc2[2 * c][ct] + cor2[2 * c][ct]) * u2[ct] + bias0),
-                            relu4((acc2[2 * c + 1][ct] + cor2[2 * c + 1][ct]) * u2[ct] + bias1), s2[ct], pls[c][ct]);
+                split_act<PL>(relu4((acc2[2 * c][ct] + cor2[2 * c][ct]) * u2[ct] + bias0),
+                              relu4((acc2[2 * c + 1][ct] + cor2[2 * c + 1][ct]) * u2[ct] + bias1), s2[ct], pls[c][ct]);
             }
         }
     }
@@ -1018,8 +1137,7 @@ __device__ __forceinline__ void head_trunk_x3(const gp_head_weights& w, const fl
     for (int c = 0; c < CPW; ++c)
 #pragma unroll
         for (int ct = 0; ct < NT; ++ct)
-#pragma unroll
-            for (int p = 0; p < X3P; ++p) act2h[(((T2[2 * c] >> 1) * NT + ct) * X3P + p) * 64 + lane] = pls[c][ct][p];
+            store_act<PL, NT>(act2h, T2[2 * c] >> 1, ct, lane, pls[c][ct]);
 #else
     if constexpr (SM::kAliasAct) __syncthreads();   // act2 overwrites act1: all reads done
 #pragma unroll
@@ -1030,10 +1148,10 @@ __device__ __forceinline__ void head_trunk_x3(const gp_head_weights& w, const fl
         for (int ct = 0; ct < NP; ++ct) {
             f16x8 pl[X3P];
             if constexpr (!JVP) {
-                split3_pair(relu4((acc2[2 * c][ct] + cor2[2 * c][ct]) * u2[ct] + bias0),
-                            relu4((acc2[2 * c + 1][ct] + cor2[2 * c + 1][ct]) * u2[ct] + bias1), s2[ct], pl);
-#pragma unroll
-                for (int p = 0; p < X3P; ++p) act2h[(((Ta >> 1) * NT + ct) * X3P + p) * 64 + lane] = pl[p];
+                ActPlanes<PL> ap;
+                split_act<PL>(relu4((acc2[2 * c][ct] + cor2[2 * c][ct]) * u2[ct] + bias0),
+                              relu4((acc2[2 * c + 1][ct] + cor2[2 * c + 1][ct]) * u2[ct] + bias1), s2[ct], ap);
+                store_act<PL, NT>(act2h, Ta >> 1, ct, lane, ap);
             } else {
                 constexpr int dt = JVP ? NP : 0;
                 const f32x4 pre0 = (acc2[2 * c][ct] + cor2[2 * c][ct]) * u2[ct] + bias0;
@@ -1060,29 +1178,29 @@ __device__ __forceinline__ void head_trunk_x3(const gp_head_weights& w, const fl
     // timing diagnostic: one wave per SIMD runs head layer 1 for its own output tiles and its sibling's (same
     // results), the sibling idles -- the single-wave stream rate inside the kernel
     if (wid < WV / 2) {
-        head_x3_head<0, NT, WV, TPW, DH, JVP>(WH, act2h, RP, RT, vo, sm, uh, sh, wid, lane, ringh, tpv, pov, pv);
+        head_x3_head<0, NT, WV, TPW, DH, JVP, PL>(WH, act2h, RP, RT, vo, sm, uh, sh, wid, lane, ringh, tpv, pov, pv);
         PC_MARK(13);
-        head_x3_head<1, NT, WV, TPW, DH, JVP>(WH, act2h, RP, RT, vo, sm, uh, sh, wid, lane, ringh, tpv, pov, pv);
+        head_x3_head<1, NT, WV, TPW, DH, JVP, PL>(WH, act2h, RP, RT, vo, sm, uh, sh, wid, lane, ringh, tpv, pov, pv);
         PC_MARK(14);
-        head_x3_head<2, NT, WV, TPW, DH, JVP>(WH, act2h, RP, RT, vo, sm, uh, sh, wid, lane, ringh, tpv, pov, pv);
+        head_x3_head<2, NT, WV, TPW, DH, JVP, PL>(WH, act2h, RP, RT, vo, sm, uh, sh, wid, lane, ringh, tpv, pov, pv);
         const int vw = wid + WV / 2;
         int TV[TPW];
 #pragma unroll
         for (int t = 0; t < TPW; ++t) TV[t] = vw * TPW + t;
-        stream_x3_step<0, DH, TPW, NT, DH>(WH, TV, act2h, lane, voff, ringh, acc2, cor2);
+        stream_x3_step<PL, 0, DH, TPW, NT, DH>(WH, TV, act2h, lane, voff, ringh, acc2, cor2);
         head_x3_init_load<0, NT, TPW, NP>(RP, RT, vo, vw, lane, tpv, pov);
-        head_x3_head<0, NT, WV, TPW, DH, JVP>(WH, act2h, RP, RT, vo, sm, uh, sh, vw, lane, ringh, tpv, pov, pv);
-        head_x3_head<1, NT, WV, TPW, DH, JVP>(WH, act2h, RP, RT, vo, sm, uh, sh, vw, lane, ringh, tpv, pov, pv);
-        head_x3_head<2, NT, WV, TPW, DH, JVP>(WH, act2h, RP, RT, vo, sm, uh, sh, vw, lane, ringh, tpv, pov, pv);
+        head_x3_head<0, NT, WV, TPW, DH, JVP, PL>(WH, act2h, RP, RT, vo, sm, uh, sh, vw, lane, ringh, tpv, pov, pv);
+        head_x3_head<1, NT, WV, TPW, DH, JVP, PL>(WH, act2h, RP, RT, vo, sm, uh, sh, vw, lane, ringh, tpv, pov, pv);
+        head_x3_head<2, NT, WV, TPW, DH, JVP, PL>(WH, act2h, RP, RT, vo, sm, uh, sh, vw, lane, ringh, tpv, pov, pv);
     }
 #else
-    head_x3_head<0, NT, WV, TPW, DH, JVP>(WH, act2h, RP, RT, vo, sm, uh, sh, wid, lane, ringh, tpv, pov, pv);
+    head_x3_head<0, NT, WV, TPW, DH, JVP, PL>(WH, act2h, RP, RT, vo, sm, uh, sh, wid, lane, ringh, tpv, pov, pv);
     if constexpr (X3_HEAD_BARRIER) __syncthreads();
     PC_MARK(13);
-    head_x3_head<1, NT, WV, TPW, DH, JVP>(WH, act2h, RP, RT, vo, sm, uh, sh, wid, lane, ringh, tpv, pov, pv);
+    head_x3_head<1, NT, WV, TPW, DH, JVP, PL>(WH, act2h, RP, RT, vo, sm, uh, sh, wid, lane, ringh, tpv, pov, pv);
     if constexpr (X3_HEAD_BARRIER) __syncthreads();
     PC_MARK(14);
-    head_x3_head<2, NT, WV, TPW, DH, JVP>(WH, act2h, RP, RT, vo, sm, uh, sh, wid, lane, ringh, tpv, pov, pv);
+    head_x3_head<2, NT, WV, TPW, DH, JVP, PL>(WH, act2h, RP, RT, vo, sm, uh, sh, wid, lane, ringh, tpv, pov, pv);
 #endif
     if constexpr (X3_PRIO) __builtin_amdgcn_s_setprio(0);
     PC_MARK(5);

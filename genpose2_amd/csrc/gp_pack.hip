@@ -103,6 +103,48 @@ std::vector<uint32_t> pack_h16(const std::vector<float>& w, int n_out, int k_in,
     return out;
 }
 
+// OCP e4m3fn byte of v (|v| <= 448), round to nearest even, subnormals kept (pack.e4m3_bits)
+uint8_t e4m3_byte(float v) {
+    const float a = std::fabs(v);
+    const uint8_t sign = std::signbit(v) ? 0x80 : 0;
+    if (a == 0.f) return sign;
+    int e = std::ilogb(a);
+    if (e < -6) e = -6;
+    int m = (int)std::nearbyint(std::ldexp(a, 3 - e));   // 0..16 in units of the binade's step (default rounding: even)
+    if (m == 16) {
+        e += 1;
+        m = 8;
+    }
+    return sign | (uint8_t)(m < 8 ? m : (((e + 7) << 3) | (m - 8)));
+}
+
+// e4m3 planes of the three f16 planes of x = w * 2^e in the hybrid trunk's A order (pack.pack_q8_fragments):
+// packed[T][g][plane][half][q][i][b] with 16 half + b = 8 cc + 4 h16 + j4 the byte of
+// W[16T + i][128g + 32cc + 16 h16 + 4q + j4]; plane p times 2^{-7, 4, 16}[p]
+std::vector<uint32_t> pack_q8(const std::vector<float>& w, int n_out, int k_in, int e) {
+    const int NT = n_out / 16, KGR = k_in / 128;
+    const int pe[3] = {-7, 4, 16};
+    std::vector<uint8_t> h((size_t)n_out * k_in * 3);
+    const float s = std::ldexp(1.0f, e);
+    for (int T = 0; T < NT; ++T)
+        for (int g = 0; g < KGR; ++g)
+            for (int q = 0; q < 4; ++q)
+                for (int i = 0; i < 16; ++i)
+                    for (int byte = 0; byte < 32; ++byte) {
+                        const int cc = byte >> 3, h16 = (byte >> 2) & 1, j4 = byte & 3;
+                        float r = w[(size_t)(16 * T + i) * k_in + 128 * g + 32 * cc + 16 * h16 + 4 * q + j4] * s;
+                        for (int plane = 0; plane < 3; ++plane) {
+                            const _Float16 v = (_Float16)r;
+                            r = r - (float)v;
+                            h[((((((size_t)T * KGR + g) * 3 + plane) * 2 + (byte >> 4)) * 4 + q) * 16 + i) * 16 + (byte & 15)] =
+                                e4m3_byte(std::ldexp((float)v, pe[plane]));
+                        }
+                    }
+    std::vector<uint32_t> out(h.size() / 4);
+    std::memcpy(out.data(), h.data(), h.size());
+    return out;
+}
+
 // numpy's pairwise summation of n doubles (the inner loop of ndarray.sum along a contiguous axis)
 double np_pairwise(const double* a, int64_t n) {
     if (n < 8) {
@@ -221,7 +263,8 @@ bool pack_encoder(StateDict& sd, Packer& P, int64_t* table) {
 }
 
 // pack.pack_heads: field offsets (gp_head_weights order) in P
-bool pack_heads(StateDict& sd, Packer& P, int64_t* f) {
+// fq: offsets of the trailing gp_head_weights fields pe2_q, h1p_q (appended after the 16 reported ones)
+bool pack_heads(StateDict& sd, Packer& P, int64_t* f, int64_t* fq) {
     const std::string n = "pose_score_net.";
     const float* pe0_w = sd.get(n + "pose_encoder.0.weight", 256 * 9);
     const float* pe0_b = sd.get(n + "pose_encoder.0.bias", 256);
@@ -287,6 +330,8 @@ bool pack_heads(StateDict& sd, Packer& P, int64_t* f) {
     hsc[5] = (float)eh;
     hsc[6] = hsc[7] = 0.f;
     f[15] = P.add(hsc, 8);
+    fq[0] = P.add_bits(pack_q8(w_pe2, 256, 256, e2));
+    fq[1] = P.add_bits(pack_q8(h1_pose, 768, 256, eh));
     return true;
 }
 
@@ -305,7 +350,8 @@ bool pack_scale(StateDict& sd, Packer& P, int64_t* f) {
 }
 
 int pack_all(int kind, int n, const char* const* names, const float* const* data, const int64_t* numel, Packer& P,
-             int64_t* fields, int64_t* enc_table) {
+             int64_t* fields, int64_t* enc_table, int64_t* fq) {
+    fq[0] = fq[1] = -1;
     GP_REQUIRE(kind >= GP_MODEL_SCORE && kind <= GP_MODEL_SCALE, "weights_pack: kind %d", kind);
     GP_REQUIRE(n >= 0 && (n == 0 || (names && data && numel)), "weights_pack: null arrays");
     StateDict sd;
@@ -321,7 +367,7 @@ int pack_all(int kind, int n, const char* const* names, const float* const* data
         ok = pack_scale(sd, P, fields + GP_PACK_SCALE);
     } else {
         fields[GP_PACK_ENC] = 0;
-        ok = pack_encoder(sd, P, enc_table) && pack_heads(sd, P, fields + GP_PACK_HEADS);
+        ok = pack_encoder(sd, P, enc_table) && pack_heads(sd, P, fields + GP_PACK_HEADS, fq);
     }
     if (!ok) {
         gp_set_error("weights_pack: state dict entry %s", sd.missing.c_str());
@@ -346,7 +392,8 @@ extern "C" int gp_weights_pack_host(int kind, int n, const char* const* names, c
                                     int64_t* fields, int64_t* enc_table) {
     GP_REQUIRE(need_floats && fields && enc_table, "weights_pack_host: null outputs");
     Packer P;
-    const int rc = pack_all(kind, n, names, data, numel, P, fields, enc_table);
+    int64_t fq[2];
+    const int rc = pack_all(kind, n, names, data, numel, P, fields, enc_table, fq);
     if (rc) return rc;
     *need_floats = P.buf.size();
     if (out) {
@@ -362,9 +409,9 @@ extern "C" int gp_weights_pack(int kind, int n, const char* const* names, const 
     GP_REQUIRE(out, "weights_pack: null out");
     *out = nullptr;
     Packer P;
-    int64_t fields[GP_PACK_NFIELDS];
+    int64_t fields[GP_PACK_NFIELDS], fq[2];
     gp_weights* w = new gp_weights();
-    int rc = pack_all(kind, n, names, data, numel, P, fields, w->table);
+    int rc = pack_all(kind, n, names, data, numel, P, fields, w->table, fq);
     if (rc) {
         delete w;
         return rc;
@@ -385,6 +432,9 @@ extern "C" int gp_weights_pack(int kind, int n, const char* const* names, const 
     } else {
         const float** h = reinterpret_cast<const float**>(&w->heads);
         for (int i = 0; i < 16; ++i) h[i] = at(fields[GP_PACK_HEADS + i]);
+        w->heads.pe2_q = at(fq[0]);   // the PC step's hybrid form (gp_head.h X3Q), and the score evaluation's
+        w->heads.h1p_q = at(fq[1]);
+        w->heads.q8_flags = GP_Q8_EVAL;
     }
     *out = w;
     return GP_OK;

@@ -145,7 +145,12 @@ extern "C" int gp_score_eval(const gp_head_weights* w, const float* pobj, const 
                              const float* x, int rows, int k, float* score, hipStream_t stream) {
     GP_REQUIRE(w && pobj && tproj_row && x && score && rows >= 0 && k >= 1, "score_eval: bad arguments");
     if (!rows) return GP_OK;
-    if (w->pe2_h)
+    // the trunk gp_pc_sample runs on this many rows: the hybrid form where it takes it
+    if (w->pe2_h && (w->q8_flags & GP_Q8_EVAL) && w->pe2_q && w->h1p_q &&
+        ((w->q8_flags & GP_Q8_ALL_TILES) || head_pick_nt(rows, true) == 4))
+        hipLaunchKernelGGL((head_eval_kernel<0, X3Q>), dim3((rows + 15) / 16), dim3(EVAL_WV * 64), 0, stream, *w, pobj, tproj_row,
+                       sigma, x, rows, k, score);
+    else if (w->pe2_h)
         hipLaunchKernelGGL((head_eval_kernel<0, X3P>), dim3((rows + 15) / 16), dim3(EVAL_WV * 64), 0, stream, *w, pobj, tproj_row,
                        sigma, x, rows, k, score);
     else
@@ -692,6 +697,9 @@ static int pc_sample_impl(const gp_head_weights* w, const float* pobj, const flo
     // split-f16 GEMMs when the packed planes are given (gp_head_weights), exact fp32 otherwise
     const bool split = w->pe2_h != nullptr;
     GP_REQUIRE(!split || (w->h1p_h && w->hsc), "pc_sample: pe2_h, h1p_h and hsc must be given together");
+    // the hybrid form (three smallest products on block-scaled FP8 MFMA) when the e4m3 planes are given too
+    GP_REQUIRE((w->pe2_q != nullptr) == (w->h1p_q != nullptr), "pc_sample: pe2_q and h1p_q must be given together");
+    const bool q8 = split && gw == nullptr && w->pe2_q != nullptr && (nt == 4 || (w->q8_flags & GP_Q8_ALL_TILES));
     PCArgs a;
     a.w = *w;
     a.pobj = pobj;
@@ -732,6 +740,12 @@ static int pc_sample_impl(const gp_head_weights* w, const float* pobj, const flo
             ag.gw = *gw;
             hipLaunchKernelGGL((pc_step_kernel<1, PC_WV1, 0, true>), grid, dim3(PC_WV1 * 64), 0, stream, ag, i, cur, prev);
         }
+        else if (q8 && nt == 4)
+            hipLaunchKernelGGL((pc_step_kernel<4, PC_WV1, X3Q>), grid, dim3(PC_WV1 * 64), 0, stream, a, i, cur, prev);
+        else if (q8 && nt == 2)
+            hipLaunchKernelGGL((pc_step_kernel<2, PC_WV1, X3Q>), grid, dim3(PC_WV1 * 64), 0, stream, a, i, cur, prev);
+        else if (q8)
+            hipLaunchKernelGGL((pc_step_kernel<1, PC_WV1, X3Q>), grid, dim3(PC_WV1 * 64), 0, stream, a, i, cur, prev);
         else if (nt == 4)
             hipLaunchKernelGGL((pc_step_kernel<4, PC_WV1, X3P>), grid, dim3(PC_WV1 * 64), 0, stream, a, i, cur, prev);
         else if (nt == 2)

@@ -207,6 +207,9 @@ class EncoderModel:
         return out
 
 
+PC_SMALL_DEFAULT = "auto"   # form of the PC step's three smallest products when GENPOSE2_PC_SMALL is unset
+
+
 class HeadModel:
     """PoseScoreNet / PoseEnergyNet heads (Rx_Ry_and_T) on device."""
 
@@ -214,6 +217,11 @@ class HeadModel:
         self.lib = _lib.load()
         self.device = device
         self.up = _Uploaded(pack.pack_heads(sd), device)
+        # GENPOSE2_PC_SMALL=f16|fp8|auto, read once here: the form of the PC step's three smallest products
+        # (set_pc_small)
+        self.pc_small = os.environ.get("GENPOSE2_PC_SMALL") or PC_SMALL_DEFAULT
+        if self.pc_small not in ("f16", "fp8", "auto"):
+            raise ValueError(f"GENPOSE2_PC_SMALL={self.pc_small!r} (f16 | fp8 | auto)")
         self.set_arith(os.environ.get("GENPOSE2_HEAD_ARITH", "f16x3"))
         self._pc_ws: Optional[torch.Tensor] = None
         self._gw = None                                    # (buffers, HeadGradWeights)
@@ -250,8 +258,22 @@ class HeadModel:
         ptrs = {k: self.up.ptr(k) for k in pack.HEAD_FIELDS}
         if arith == "f32":
             ptrs.update(pe2_h=None, h1p_h=None, hsc=None)
+        elif self.pc_small != "f16":   # _lib.HeadWeights.q8_flags: 1 score() follows, 2 every tile width
+            ptrs.update({k: self.up.ptr(k) for k in pack.HEAD_Q8_FIELDS}, q8_flags=3 if self.pc_small == "fp8" else 1)
         self.arith = arith
         self.w = _lib.HeadWeights(**ptrs)
+
+    def set_pc_small(self, form: str) -> None:
+        """The PC step's products of plane order 2 (w_hi*a_lo, w_mid*a_mid, w_lo*a_hi) under "f16x3": "f16" (f16
+        MFMA, the six-product form), "fp8" (OCP e4m3 planes on block-scaled FP8 MFMA, gp_head.h X3Q) or "auto"
+        (the default: fp8 where the step runs 64-candidate tiles, from 8,193 rows, where it measured faster; f16
+        on narrower tiles, where it measured slower). score() evaluates the trunk the PC step runs on that many
+        rows, so it follows (its result equals the step's own score bit for bit, and the hybrid's error is
+        measured through it); the energy, divergence, gradient and ODE kernels keep the six f16 products."""
+        if form not in ("f16", "fp8", "auto"):
+            raise ValueError(f"unknown form {form!r} (f16 | fp8 | auto)")
+        self.pc_small = form
+        self.set_arith(self.arith)
 
     def _s(self):
         return ctypes.c_void_p(stream_handle(self.device))

@@ -162,6 +162,59 @@ def pack_h16_fragments(w: np.ndarray, e: int, planes: int = 2) -> np.ndarray:
 
 HEAD_PLANES = 3   # f16 planes per weight of the head trunk's GEMMs (pe2_h, h1p_h)
 
+# The hybrid form of the PC step's GEMMs (gp_head.h, X3Q): e4m3 planes of the three f16 planes, each the f16
+# plane times a constant power of two that brings the plane's bound into e4m3's normal range below its
+# maximum 448 (w * 2**e has max in [2**14, 2**15): hi < 2**15, |mid| <= 2**3, |lo| <= 2**-9).
+HEAD_Q8_FIELDS = ("pe2_q", "h1p_q")
+Q8_PLANE_EXPONENTS = (-7, 4, 16)   # hi, mid, lo
+
+
+def e4m3_bits(x: np.ndarray) -> np.ndarray:
+    """OCP e4m3fn bytes of x (|x| <= 448), round to nearest even, subnormals kept (v_cvt_pk_fp8_f32)."""
+    x = np.asarray(x, np.float64)
+    a = np.abs(x)
+    assert float(a.max(initial=0.0)) <= 448.0
+    e = np.maximum(np.floor(np.log2(np.where(a > 0, a, 1.0))), -6.0)
+    m = np.rint(a / np.exp2(e - 3)).astype(np.int64)           # 0..16 in units of the binade's step
+    e = np.where(m == 16, e + 1, e).astype(np.int64)
+    m = np.where(m == 16, 8, m)
+    bits = np.where(m < 8, m, ((e + 7) << 3) | (m - 8))         # m < 8: subnormal (exponent field 0)
+    return (bits | (np.signbit(x).astype(np.int64) << 7)).astype(np.uint8)
+
+
+def e4m3_value(b: np.ndarray) -> np.ndarray:
+    """The float64 values of OCP e4m3fn bytes (no NaN handling: the planes hold none)."""
+    b = np.asarray(b, np.uint8).astype(np.int64)
+    ex, m = (b >> 3) & 15, b & 7
+    v = np.where(ex == 0, m * 2.0 ** -9, (8 + m) * np.exp2(ex - 10.0))
+    return np.where(b & 128, -v, v)
+
+
+def pack_q8_fragments(w: np.ndarray, e: int) -> np.ndarray:
+    """(n_out, k_in) -> int32 words of the e4m3 planes of the three f16 planes of x = w * 2**e, in the A-operand
+    order the hybrid trunk feeds v_mfma_scale_f32_16x16x128_f8f6f4 (k_in a multiple of 128):
+
+        packed[T][g][plane][half][lane][b] = e4m3(plane(W[16T + (lane & 15)][128g + 32cc + 16*(j // 4) + 4*(lane >> 4) + j % 4])
+                                                  * 2**Q8_PLANE_EXPONENTS[plane]),   8*cc + j = 16*half + b
+
+    i.e. a lane's 32 bytes of group g are its four f16 fragments (pack_h16_fragments) of chunks 4g..4g+3, one
+    byte per element; plane 0, 1, 2 = hi, mid, lo. One (T, g, plane) is 2 KiB, one half 1 KiB."""
+    n_out, k_in = w.shape
+    assert n_out % 16 == 0 and k_in % 128 == 0, (n_out, k_in)
+    r = (np.asarray(w, np.float32) * np.float32(2.0 ** e)).astype(np.float32)
+    ps = []
+    for ex in Q8_PLANE_EXPONENTS:
+        h = r.astype(np.float16)
+        ps.append(e4m3_bits(h.astype(np.float64) * 2.0 ** ex))
+        r = (r - h.astype(np.float32)).astype(np.float32)
+    NT, KGR = n_out // 16, k_in // 128
+
+    def frag(p):   # [T][i][g][cc][half16][q][j4] -> [T][g][q][i][cc][half16][j4]: lane = 16q + i, byte = 8cc + 4 half16 + j4
+        return p.reshape(NT, 16, KGR, 4, 2, 4, 4).transpose(0, 2, 5, 1, 3, 4, 6).reshape(NT, KGR, 64, 2, 16)
+    out = np.stack([frag(p) for p in ps], axis=2)               # [T][g][plane][lane][half][16]
+    out = out.transpose(0, 1, 2, 4, 3, 5)                       # [T][g][plane][half][lane][16]
+    return np.ascontiguousarray(out).reshape(-1).view(np.int32)
+
 
 def split_constants(p: Dict[str, np.ndarray], e2: int, eh: int) -> np.ndarray:
     """hsc: bounds the split trunk derives its per-candidate activation exponents from
@@ -196,6 +249,8 @@ def pack_heads(sd: weights.StateDict) -> Dict[str, np.ndarray]:
     e2, eh = split_exponent(p["pe2_w"]), split_exponent(h1_pose)
     out["pe2_h"] = pack_h16_fragments(p["pe2_w"], e2, HEAD_PLANES)
     out["h1p_h"] = pack_h16_fragments(h1_pose, eh, HEAD_PLANES)
+    out["pe2_q"] = pack_q8_fragments(p["pe2_w"], e2)
+    out["h1p_q"] = pack_q8_fragments(h1_pose, eh)
     out["hsc"] = np.asarray(split_constants(p, e2, eh), np.float32)
     return out
 

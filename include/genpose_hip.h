@@ -211,7 +211,20 @@ typedef struct {
     const void *pe2_h;
     const void *h1p_h;
     const float *hsc;
+    /* Hybrid form of the PC step's two GEMMs (additive, trailing: a caller that leaves them zero gets the six
+     * f16 products everywhere): OCP e4m3 planes of the f16 planes above (pack.py pack_q8_fragments: w_hi x 2^-7,
+     * w_mid x 2^4, w_lo x 2^16, 3 bytes per weight, in the A order of v_mfma_scale_f32_16x16x128_f8f6f4). Both
+     * given: gp_pc_sample / gp_pc_sample_global form hi*hi, hi*mid and mid*hi on f16 MFMA and the three
+     * products of plane order 2 on block-scaled FP8 MFMA (gp_head.h, X3Q) where they run 64-candidate tiles
+     * (rows >= 8193; narrower tiles are bound by the weight stream, which the hybrid form makes 7/6 as long, and
+     * measured slower); every other kernel keeps the six f16 products. q8_flags: GP_Q8_EVAL routes gp_score_eval
+     * through the trunk gp_pc_sample runs on that many rows, so that it returns the PC step's own score bit for
+     * bit (the loaders set it with the planes); GP_Q8_ALL_TILES takes the hybrid form at every tile width. */
+    const void *pe2_q;
+    const void *h1p_q;
+    size_t q8_flags;
 } gp_head_weights;
+enum { GP_Q8_EVAL = 1, GP_Q8_ALL_TILES = 2 };
 
 /* Per-object projection P[b] = W1_pts . pts_feat[b] + b1 -> pobj (b,768). */
 int gp_head_object_proj(const gp_head_weights *w, const float *pts_feat, int b, float *pobj,
