@@ -2,6 +2,8 @@
 // Used by the PC sampler / score / energy kernels (gp_score.hip) and the ODE stage kernels
 // (gp_ode.hip). Reference: PoseScoreNet.forward (networks/gf_algorithms/scorenet.py:215-275).
 #pragma once
+#include <type_traits>
+
 #include "gp_common.h"
 
 constexpr int HT = 256;          // threads per workgroup
@@ -66,12 +68,11 @@ struct HeadSmem {
     f32x4 cscl[NT * 16][2];            // split trunk: per-column scales {s1, s2, u2, uh}, {sh} (ColScales)
 };
 
-// Threads [FIRST, WV*64) copy the small weights into LDS.
-// PE0 = false: pose_encoder.0's fragments and bias are not staged (the split trunk holds them in
-// registers from kernel entry, SplitScalars).
-template <int NT, int WV, int FIRST = 0, bool PE0 = true, int PL>
+// Threads [FIRST, WV*64) copy the small weights into LDS. pose_encoder.0's fragments and bias are staged
+// for the exact-fp32 trunk only (the split trunk holds them in registers from kernel entry, SplitScalars).
+template <int FIRST = 0, int NT, int WV, int PL>
 __device__ __forceinline__ void stage_small_weights(const gp_head_weights& w, HeadSmem<NT, WV, PL>& sm) {
-    static_assert(PE0 || PL, "the fp32 trunk reads pose_encoder.0 from LDS");
+    constexpr bool PE0 = PL == 0;
     constexpr int NTH = WV * 64 - FIRST;
     const int t0 = (int)threadIdx.x - FIRST;
     if (t0 < 0) return;
@@ -86,14 +87,15 @@ __device__ __forceinline__ void stage_small_weights(const gp_head_weights& w, He
 }
 
 // Head output o of column c (valid after head_trunk): bias + the per-wave partials in wave order.
-template <int NT, int WV, int PL>
+// TAN: c is a tangent column of a JVP trunk (below), its output (d head / d pose) . eps has no bias.
+template <bool TAN = false, int NT, int WV, int PL>
 __device__ __forceinline__ float head_out(const HeadSmem<NT, WV, PL>& sm, int c, int o) {
     const int h = o / 3;
     const int v = (h * NT + (c >> 4)) * 3 + (o - 3 * h);
     float acc = 0.f;
 #pragma unroll
     for (int w = 0; w < WV; ++w) acc += sm.red[v][c & 15][w];
-    return sm.h2b[o] + acc;
+    return TAN ? acc : sm.h2b[o] + acc;
 }
 
 __device__ __forceinline__ void wave_sync() {
@@ -107,7 +109,8 @@ __device__ __forceinline__ void wave_sync() {
 // so that the loads of k-group g+D are in flight while k-group g feeds the MFMAs; B fragments
 // come from LDS. Loads are raw buffer loads: the tile/k-group offset is a wave-uniform SGPR
 // (soffset) and the only per-lane address is lane*16 (voffset), so the fully unrolled ring needs
-// no 64-bit address registers. Every ring index is a compile-time constant.
+// no 64-bit address registers. The k-group loop is unrolled by template recursion, so every ring
+// index is a compile-time constant (no scratch).
 // Steps G..GEND-1 of the pipelined stream (step G issues k-group G's loads and computes k-group
 // G-D). Steps 0..D-1 only prime the ring, so they can be issued early (before a barrier).
 template <int G, int GEND, int TT, int NT, int KG, int D>
@@ -140,39 +143,15 @@ __device__ __forceinline__ void stream_step(__amdgpu_buffer_rsrc_t W, const int 
     }
 }
 
-// acc[t][ct] += sum_g A(tile T[t], k-group g) . B(k-group g, column tile ct) over KG k-groups.
-// A fragments stream from global (L2-resident packed weights) through a (D+1)-slot register ring
-// so that the loads of k-group g+D are in flight while k-group g feeds the MFMAs; B fragments
-// come from LDS. Loads are raw buffer loads: the tile/k-group offset is a wave-uniform SGPR
-// (soffset) and the only per-lane address is lane*16 (voffset). The k-group loop is unrolled by
-// template recursion, so every ring index is a compile-time constant (no scratch).
-template <int TT, int NT, int KG, int D>
-__device__ __forceinline__ void stream_layer(__amdgpu_buffer_rsrc_t W, const int (&T)[TT],
-                                             const f32x4* __restrict__ B, int lane, f32x4 (&acc)[TT][NT]) {
-    f32x4 ring[D + 1][TT];
-    stream_step<0, KG + D, TT, NT, KG, D>(W, T, B, lane, lane * 16, ring, acc);
-}
-
 // Forward-mode derivative (JVP) trunks: the upper half of the column tiles (ct >= NT / 2) carries a tangent
 // of the lower half's poses (column c + 8 NT is the tangent of column c; its xin row is the direction eps).
 // A tangent tile runs through the same GEMMs on the same weight fragments as its primal tile, without the
 // bias / pobj / tproj terms, and takes each ReLU's mask from the primal's pre-activation (torch: relu' = 0
-// at 0): it sits in the same lane and accumulator slot, so the mask needs no exchange. head_out_tan then
+// at 0): it sits in the same lane and accumulator slot, so the mask needs no exchange. head_out<true> then
 // gives (d head / d pose) . eps.
 __device__ __forceinline__ f32x4 mask4(f32x4 d, f32x4 pre) {
     return f32x4{pre.x > 0.f ? d.x : 0.f, pre.y > 0.f ? d.y : 0.f, pre.z > 0.f ? d.z : 0.f, pre.w > 0.f ? d.w : 0.f};
 }
-// Tangent head output o of tangent column c (JVP trunks): the per-wave partials in wave order, no bias.
-template <int NT, int WV, int PL>
-__device__ __forceinline__ float head_out_tan(const HeadSmem<NT, WV, PL>& sm, int c, int o) {
-    const int h = o / 3;
-    const int v = (h * NT + (c >> 4)) * 3 + (o - 3 * h);
-    float acc = 0.f;
-#pragma unroll
-    for (int w = 0; w < WV; ++w) acc += sm.red[v][c & 15][w];
-    return acc;
-}
-
 // Reverse-pass buffers of the energy-gradient kernels (head_trunk<.., GRAD>, head_backward): cotangents in the
 // B-operand layout, [k-group][lane]. g1 (the cotangent of pose_encoder.0's output) takes gh's first 16
 // k-groups and the per-wave partials of the pose gradient take g2's: each is written after a barrier that
@@ -525,21 +504,26 @@ struct SplitScalars {
     int ew2, ewh;
     f32x4 pe0a[4], pe0b[4];   // this wave's 16 / WV output tiles (entries past them unused)
 };
-template <int WV = HSPLIT_WV>
+// PL = 0 (the exact-fp32 trunk, which has none): zeros, nothing loaded.
+template <int PL, int WV = HSPLIT_WV>
 __device__ __forceinline__ SplitScalars load_split_scalars(const gp_head_weights& w) {
     static_assert(WV == 4 || WV == 8, "the split trunk runs 4- or 8-wave workgroups");
-    const f32x4 a = ld4(w.hsc), b = ld4(w.hsc + 4);
-    SplitScalars r{a.x, a.y, a.z, a.w, (int)b.x, (int)b.y, {}, {}};
-    const int tid = tid_x();
-    const int lane = tid & 63, q = lane >> 4;
-    const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+    if constexpr (PL == 0) {
+        return SplitScalars{};
+    } else {
+        const f32x4 a = ld4(w.hsc), b = ld4(w.hsc + 4);
+        SplitScalars r{a.x, a.y, a.z, a.w, (int)b.x, (int)b.y, {}, {}};
+        const int tid = tid_x();
+        const int lane = tid & 63, q = lane >> 4;
+        const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
 #pragma unroll
-    for (int t = 0; t < 16 / WV; ++t) {
-        const int T = wid * (16 / WV) + t;
-        r.pe0a[t] = ld4(w.pe0_w + ((size_t)T * 64 + lane) * 4);
-        r.pe0b[t] = ld4(w.pe0_b + 16 * T + 4 * q);
+        for (int t = 0; t < 16 / WV; ++t) {
+            const int T = wid * (16 / WV) + t;
+            r.pe0a[t] = ld4(w.pe0_w + ((size_t)T * 64 + lane) * 4);
+            r.pe0b[t] = ld4(w.pe0_b + 16 * T + 4 * q);
+        }
+        return r;
     }
-    return r;
 }
 
 // Sums of four values over the four 16-lane rows, scattered: on return row q of the wave holds the
@@ -556,12 +540,6 @@ __device__ __forceinline__ float rows_sum_scatter4(float a, float b, float c, fl
     const auto st = __builtin_amdgcn_permlane32_swap(__float_as_uint(s), __float_as_uint(t), false, false);
     return __uint_as_float(st[0]) + __uint_as_float(st[1]);            // rows: a, b, c, d
 }
-
-// ReLU -> head layer 2 (block diagonal 3 x (256 -> 3)) partials of the split trunk's head-layer-1
-// accumulators (scaled domain; uh[ct] undoes the scale, a power of two, so scaling each lane's chain
-// before the row sum is exact). Each (column, output) is one fp32 FMA chain over this wave's channels,
-// t-major then j, with separately rounded sums across rows and waves (head_out). Scalar FMAs: the
-// same chains as v_pk_fma_f32 over column-tile pairs (broadcast weights through op_sel, results in
 
 // A candidate's power-of-two scales of the split trunk from m0 = max |pose entry| (rigorous bounds of
 // pose_encoder.0's and .2's outputs, hs): s1 / s2 scale the two activations into [2^14, 2^15) at their
@@ -606,29 +584,6 @@ __device__ __forceinline__ float xin_row_absmax(f32x4 b) {
 #endif
 #ifndef X3_DH
 #define X3_DH 1                  // 32-deep chunks of head-layer-1 weights kept in flight (2: ab_prio_dh1.json)
-#endif
-#ifndef X3_PRIO
-#define X3_PRIO 0                // 1: alternate the issue priority of a SIMD's two waves per chunk (tuning)
-#endif
-#ifndef X3_BPIPE
-#define X3_BPIPE 1               // B planes read one column tile ahead of their MFMAs (0: just in time;
-                                 // profiles/r4/ab_bpipe.json)
-#endif
-#ifndef X3_CHAIN
-#define X3_CHAIN 1               // each tile's correction products back to back (R=25,600 -3 %, R=12,800 even;
-                                 // profiles/r4/ab_chain.json)
-#endif
-#ifndef X3_EPI_EARLY
-#define X3_EPI_EARLY 1           // pose_encoder.2 epilogue planes computed before the alias barrier
-                                 // (profiles/r4/ab_epi_early.json)
-#endif
-#ifndef X3_DIAG
-#define X3_DIAG 0                // timing diagnostics only (wrong results), bits: 1 no B-plane LDS reads after
-                                 // the first, 2 no weight loads after the ring's priming, 4 no head-layer-2
-                                 // epilogue between the heads
-#endif
-#ifndef X3_HEAD_BARRIER
-#define X3_HEAD_BARRIER 0        // 1: a workgroup barrier after each head of head layer 1 (tuning)
 #endif
 constexpr int X3P = 3;           // planes per operand
 
@@ -743,12 +698,11 @@ __device__ __forceinline__ void store_act(f16x8* act, int chunk, int ct, int lan
             reinterpret_cast<u32x2*>(act + act_q8<NT>(chunk >> 2, ct, k, cc >> 1) + lane)[cc & 1] = a.q[k];
     }
 }
-
 // One pipelined step of a 256-deep f16x3 layer: step G issues the loads of chunk G (tile T[t]'s three
 // weight planes, 3 KiB per tile: pack_h16_fragments' [T][c][plane][lane]) and computes chunk G - D from
 // the ring; B = activation planes in LDS, [chunk][ct][plane][lane]. acc += hi*hi, cor += the five cross
 // products, smallest first. The B planes of column tile ct + 1 are read while column tile ct's MFMAs
-// run (X3_BPIPE; sched barriers keep the compiler from sinking the reads to their first use, where
+// run (sched barriers keep the compiler from sinking the reads to their first use, where
 // each became an lgkmcnt(0) stall). Steps 0..D-1 only prime the ring (no B or accumulator access), so
 // they can run before a barrier or under another phase.
 // PL = X3Q (hybrid): a ring slot holds the chunk's hi and mid planes and, for a chunk that carries a product
@@ -790,7 +744,7 @@ __device__ __forceinline__ void stream_x3_rec(__amdgpu_buffer_rsrc_t W, __amdgpu
                                               f32x4 (&cor)[TT][NT], f16x8 (&bc)[ring_planes<PL>()]) {
     constexpr int RP = ring_planes<PL>();
     if constexpr (G < GEND) {
-        if constexpr (G < KC_HID && ((X3_DIAG & 2) == 0 || G < D + 1)) {
+        if constexpr (G < KC_HID) {
 #pragma unroll
             for (int t = 0; t < TT; ++t) {
 #pragma unroll
@@ -808,38 +762,22 @@ __device__ __forceinline__ void stream_x3_rec(__amdgpu_buffer_rsrc_t W, __amdgpu
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (G >= D) {
             constexpr int GG = G - D, S = GG % (D + 1), KQ = GG & 3;
-#if X3_PRIO
-            // the two waves of a SIMD (w, w + 4) take turns at issue priority chunk by chunk, so neither runs
-            // a whole stream ahead and leaves the other to finish it alone (tuning variant)
-            if ((__builtin_amdgcn_readfirstlane(threadIdx.x >> 8) ^ GG) & 1)
-                __builtin_amdgcn_s_setprio(1);
-            else
-                __builtin_amdgcn_s_setprio(0);
-#endif
-#if X3_BPIPE
             // B planes one column tile ahead: column tile ct + 1's (or the next chunk's first) reads are in
-            // flight during column tile ct's MFMAs
+            // flight during column tile ct's MFMAs (just-in-time reads: profiles/r4/ab_bpipe.json)
             if constexpr (GG == 0) load_b_planes<PL, NT>(B, 0, 0, lane, bc);
 #pragma unroll
             for (int ct = 0; ct < NT; ++ct) {
                 f16x8 bn[RP];
                 const int ng = ct + 1 < NT ? GG : GG + 1, nc = ct + 1 < NT ? ct + 1 : 0;
-                if ((X3_DIAG & 1) == 0 && (ct + 1 < NT || GG + 1 < KC_HID)) load_b_planes<PL, NT>(B, ng, nc, lane, bn);
-#if X3_DIAG & 1
-#pragma unroll
-                for (int p = 0; p < RP; ++p) {   // distinct operands per tile, so the MFMAs stay distinct
-                    using u4 = __attribute__((ext_vector_type(4))) unsigned;
-                    bn[p] = __builtin_bit_cast(f16x8, __builtin_bit_cast(u4, bc[p]) ^ (unsigned)(ng * NT + nc + 1));
-                }
-#endif
+                if (ct + 1 < NT || GG + 1 < KC_HID) load_b_planes<PL, NT>(B, ng, nc, lane, bn);
                 __builtin_amdgcn_sched_barrier(0);   // the reads stay ahead of this column tile's MFMAs
                 f16x8 b[RP];
 #pragma unroll
                 for (int p = 0; p < RP; ++p) b[p] = bc[p];
-#if X3_CHAIN
                 // each tile's correction products back to back on one accumulator, then the main
                 // products (the issue rate itself does not depend on the order, scripts/mfma_chain_probe.hip;
-                // this order measured 3 % faster at two passes, even at one)
+                // this order measured 3 % faster at R=25,600 (two passes), even at R=12,800 (one):
+                // profiles/r4/ab_chain.json)
 #pragma unroll
                 for (int t = 0; t < TT; ++t) {
                     cor[t][ct] = cross_products<PL, KQ>(ring[S][t], b, cor[t][ct]);
@@ -847,31 +785,12 @@ __device__ __forceinline__ void stream_x3_rec(__amdgpu_buffer_rsrc_t W, __amdgpu
                 }
 #pragma unroll
                 for (int t = 0; t < TT; ++t) acc[t][ct] = mfma_h(ring[S][t][0], b[0], acc[t][ct]);
-#else
-#pragma unroll
-                for (int t = 0; t < TT; ++t) {
-                    cor[t][ct] = cross_products<PL, KQ>(ring[S][t], b, cor[t][ct]);
-                    acc[t][ct] = mfma_h(ring[S][t][0], b[0], acc[t][ct]);
-                }
-#endif
                 __builtin_amdgcn_sched_barrier(0);
                 if (ct + 1 < NT || GG + 1 < KC_HID) {
 #pragma unroll
                     for (int p = 0; p < RP; ++p) bc[p] = bn[p];
                 }
             }
-#else
-#pragma unroll
-            for (int ct = 0; ct < NT; ++ct) {
-                f16x8 b[RP];
-                load_b_planes<PL, NT>(B, GG, ct, lane, b);
-#pragma unroll
-                for (int t = 0; t < TT; ++t) {
-                    cor[t][ct] = cross_products<PL, KQ>(ring[S][t], b, cor[t][ct]);
-                    acc[t][ct] = mfma_h(ring[S][t][0], b[0], acc[t][ct]);
-                }
-            }
-#endif
         }
         stream_x3_rec<PL, G + 1, GEND, TT, NT, D>(W, WQ, T, B, lane, voff, ring, acc, cor, bc);
     }
@@ -884,7 +803,7 @@ template <int PL, int G, int GEND, int TT, int NT, int D>
 __device__ __forceinline__ void stream_x3_step(const X3Weights& w, const int (&T)[TT], const f16x8* __restrict__ B,
                                                int lane, int voff, f16x8 (&ring)[D + 1][TT][ring_planes<PL>()],
                                                f32x4 (&acc)[TT][NT], f32x4 (&cor)[TT][NT]) {
-    f16x8 bc[ring_planes<PL>()];   // X3_BPIPE: the B planes of the next column tile, carried from step to step
+    f16x8 bc[ring_planes<PL>()];   // the B planes of the next column tile, carried from step to step
     stream_x3_rec<PL, G, GEND, TT, NT, D>(w.W, w.WQ, T, B, lane, voff, ring, acc, cor, bc);
 }
 
@@ -931,12 +850,8 @@ __device__ __forceinline__ void head_x3_head(const X3Weights& WH, const f16x8* _
     for (int t = 0; t < TPW; ++t)
 #pragma unroll
         for (int ct = 0; ct < NT; ++ct) {
-            if constexpr (JVP) {
-                if (ct < NP) acc[t][ct] = (pov[t][ct < NP ? ct : 0] + tpv[t]) * sh[ct];
-                else acc[t][ct] = f32x4{0.f, 0.f, 0.f, 0.f};
-            } else {
-                acc[t][ct] = (pov[t][ct] + tpv[t]) * sh[ct];
-            }
+            if (ct < NP) acc[t][ct] = (pov[t][ct] + tpv[t]) * sh[ct];
+            else acc[t][ct] = f32x4{0.f, 0.f, 0.f, 0.f};   // a tangent tile has no init rows
             cor[t][ct] = f32x4{0.f, 0.f, 0.f, 0.f};
         }
     stream_x3_step<PL, DH, KC_HID + DH, TPW, NT, DH>(WH, TH, act2h, lane, voff, ringh, acc, cor);
@@ -950,20 +865,12 @@ __device__ __forceinline__ void head_x3_head(const X3Weights& WH, const f16x8* _
     // nothing below is scheduled into the MFMA stream above: interleaved there, the row swaps of the
     // reduce-scatter reused registers in-flight MFMAs still read (v_permlane*_swap writes both operands)
     __builtin_amdgcn_sched_barrier(0);
-    // u = ReLU(scale-undone accumulators) -> head layer 2 (3 outputs) partials: one fp32 FMA chain per
-    // (column, output) over this wave's channels, t-major then j
+    // ReLU -> head layer 2 (block diagonal 3 x (256 -> 3)) partials of this head's accumulators (scaled domain;
+    // uh[ct], a power of two, undoes the scale exactly). Each (column, output) is one fp32 FMA chain over this
+    // wave's channels, t-major then j, with separately rounded sums across rows and waves (head_out).
     float p[NT][3];
 #pragma unroll
     for (int ct = 0; ct < NT; ++ct) p[ct][0] = p[ct][1] = p[ct][2] = 0.f;
-#if X3_DIAG & 4
-    // timing diagnostic: no layer-2 epilogue between the heads' streams (every accumulator still used)
-#pragma unroll
-    for (int t = 0; t < TPW; ++t)
-#pragma unroll
-        for (int ct = 0; ct < NT; ++ct)
-#pragma unroll
-            for (int o = 0; o < 3; ++o) p[ct][o] += acc[t][ct][o] + cor[t][ct][o + 1];
-#else
 #pragma unroll
     for (int t = 0; t < TPW; ++t) {
         const int ch = 16 * (wid * TPW + t) + 4 * q;
@@ -989,7 +896,6 @@ __device__ __forceinline__ void head_x3_head(const X3Weights& WH, const f16x8* _
             }
         }
     }
-#endif
 #pragma unroll
     for (int ct = 0; ct < NT; ++ct)
 #pragma unroll
@@ -1108,9 +1014,8 @@ __device__ __forceinline__ void head_trunk_x3(const gp_head_weights& w, const fl
     for (int ct = 0; ct < NT; ++ct) vo[ct] = obj_of_col[ct * 16 + n] * (3 * HID * 4) + 16 * q;
     f32x4 tpv[TPW], pov[TPW][NP];
     head_x3_init_load<0, NT, TPW, NP>(RP, RT, vo, wid, lane, tpv, pov);
-#if X3_EPI_EARLY
     // the epilogue's planes are made before the alias barrier (a wave that finished its stream early does
-    // this VALU work while it waits for the last one) and only written after it
+    // this VALU work while it waits for the last one) and only written after it (profiles/r4/ab_epi_early.json)
     ActPlanes<PL> pls[CPW][NT];
 #pragma unroll
     for (int c = 0; c < CPW; ++c) {
@@ -1138,71 +1043,17 @@ __device__ __forceinline__ void head_trunk_x3(const gp_head_weights& w, const fl
 #pragma unroll
         for (int ct = 0; ct < NT; ++ct)
             store_act<PL, NT>(act2h, T2[2 * c] >> 1, ct, lane, pls[c][ct]);
-#else
-    if constexpr (SM::kAliasAct) __syncthreads();   // act2 overwrites act1: all reads done
-#pragma unroll
-    for (int c = 0; c < CPW; ++c) {
-        const int Ta = T2[2 * c];
-        const f32x4 bias0 = ld4(&sm.pe2b[16 * Ta + 4 * q]), bias1 = ld4(&sm.pe2b[16 * (Ta + 1) + 4 * q]);
-#pragma unroll
-        for (int ct = 0; ct < NP; ++ct) {
-            f16x8 pl[X3P];
-            if constexpr (!JVP) {
-                ActPlanes<PL> ap;
-                split_act<PL>(relu4((acc2[2 * c][ct] + cor2[2 * c][ct]) * u2[ct] + bias0),
-                              relu4((acc2[2 * c + 1][ct] + cor2[2 * c + 1][ct]) * u2[ct] + bias1), s2[ct], ap);
-                store_act<PL, NT>(act2h, Ta >> 1, ct, lane, ap);
-            } else {
-                constexpr int dt = JVP ? NP : 0;
-                const f32x4 pre0 = (acc2[2 * c][ct] + cor2[2 * c][ct]) * u2[ct] + bias0;
-                const f32x4 pre1 = (acc2[2 * c + 1][ct] + cor2[2 * c + 1][ct]) * u2[ct] + bias1;
-                split3_pair(relu4(pre0), relu4(pre1), s2[ct], pl);
-#pragma unroll
-                for (int p = 0; p < X3P; ++p) act2h[(((Ta >> 1) * NT + ct) * X3P + p) * 64 + lane] = pl[p];
-                split3_pair(mask4((acc2[2 * c][ct + dt] + cor2[2 * c][ct + dt]) * u2[ct + dt], pre0),
-                            mask4((acc2[2 * c + 1][ct + dt] + cor2[2 * c + 1][ct + dt]) * u2[ct + dt], pre1),
-                            s2[ct + dt], pl);
-#pragma unroll
-                for (int p = 0; p < X3P; ++p) act2h[(((Ta >> 1) * NT + ct + dt) * X3P + p) * 64 + lane] = pl[p];
-            }
-        }
-    }
-#endif
     __syncthreads();
     PC_MARK(4);
     // ---- head layer 1 (pose block 256 -> 3x256) head by head, each followed by its layer-2 partials
     float pv[SM::kRedV];
 #pragma unroll
     for (int v = 9 * NT; v < SM::kRedV; ++v) pv[v] = 0.f;
-#if X3_DIAG & 8
-    // timing diagnostic: one wave per SIMD runs head layer 1 for its own output tiles and its sibling's (same
-    // results), the sibling idles -- the single-wave stream rate inside the kernel
-    if (wid < WV / 2) {
-        head_x3_head<0, NT, WV, TPW, DH, JVP, PL>(WH, act2h, RP, RT, vo, sm, uh, sh, wid, lane, ringh, tpv, pov, pv);
-        PC_MARK(13);
-        head_x3_head<1, NT, WV, TPW, DH, JVP, PL>(WH, act2h, RP, RT, vo, sm, uh, sh, wid, lane, ringh, tpv, pov, pv);
-        PC_MARK(14);
-        head_x3_head<2, NT, WV, TPW, DH, JVP, PL>(WH, act2h, RP, RT, vo, sm, uh, sh, wid, lane, ringh, tpv, pov, pv);
-        const int vw = wid + WV / 2;
-        int TV[TPW];
-#pragma unroll
-        for (int t = 0; t < TPW; ++t) TV[t] = vw * TPW + t;
-        stream_x3_step<PL, 0, DH, TPW, NT, DH>(WH, TV, act2h, lane, voff, ringh, acc2, cor2);
-        head_x3_init_load<0, NT, TPW, NP>(RP, RT, vo, vw, lane, tpv, pov);
-        head_x3_head<0, NT, WV, TPW, DH, JVP, PL>(WH, act2h, RP, RT, vo, sm, uh, sh, vw, lane, ringh, tpv, pov, pv);
-        head_x3_head<1, NT, WV, TPW, DH, JVP, PL>(WH, act2h, RP, RT, vo, sm, uh, sh, vw, lane, ringh, tpv, pov, pv);
-        head_x3_head<2, NT, WV, TPW, DH, JVP, PL>(WH, act2h, RP, RT, vo, sm, uh, sh, vw, lane, ringh, tpv, pov, pv);
-    }
-#else
     head_x3_head<0, NT, WV, TPW, DH, JVP, PL>(WH, act2h, RP, RT, vo, sm, uh, sh, wid, lane, ringh, tpv, pov, pv);
-    if constexpr (X3_HEAD_BARRIER) __syncthreads();
     PC_MARK(13);
     head_x3_head<1, NT, WV, TPW, DH, JVP, PL>(WH, act2h, RP, RT, vo, sm, uh, sh, wid, lane, ringh, tpv, pov, pv);
-    if constexpr (X3_HEAD_BARRIER) __syncthreads();
     PC_MARK(14);
     head_x3_head<2, NT, WV, TPW, DH, JVP, PL>(WH, act2h, RP, RT, vo, sm, uh, sh, wid, lane, ringh, tpv, pov, pv);
-#endif
-    if constexpr (X3_PRIO) __builtin_amdgcn_s_setprio(0);
     PC_MARK(5);
     if constexpr ((3 * NT) % 4 != 0) {
 #pragma unroll
@@ -1211,6 +1062,24 @@ __device__ __forceinline__ void head_trunk_x3(const gp_head_weights& w, const fl
     }
     __syncthreads();
     PC_MARK(6);
+}
+
+// The object (row of pobj) of candidate row r; rows past the end take the last row's, which keeps their loads in bounds
+__device__ __forceinline__ int obj_of_row(int r, int rows, int kper) { return (r < rows ? r : rows - 1) / kper; }
+
+// The trunk of the form PL (taken from sm): head_trunk for 0, head_trunk_x3 otherwise. hs: load_split_scalars<PL>.
+// For the PC step, the ODE stages and the denoise kernel. The evaluation and JVP kernels select their trunk
+// themselves: through this wrapper the compiler allocated their registers differently and, in the exact-fp32 JVP
+// trunk, contracted other products of the layer-2 sums (which are not under contract(off)), so the divergence lost
+// its bits.
+template <bool PRE = false, int NT, int WV, int PL>
+__device__ __forceinline__ void run_head_trunk(const gp_head_weights& w, const float* pobj, const float* tproj,
+                                               const int* obj_of_col,
+                                               HeadSmem<NT, WV, PL>& sm, int trace_slot, const SplitScalars& hs) {
+    if constexpr (PL != 0)
+        head_trunk_x3<NT, WV, PRE>(w, pobj, tproj, obj_of_col, sm, trace_slot, hs);
+    else
+        head_trunk<NT, WV>(w, pobj, tproj, obj_of_col, sm, trace_slot);
 }
 
 // ============================================================================ tile width
@@ -1231,6 +1100,23 @@ __device__ __forceinline__ void head_trunk_x3(const gp_head_weights& w, const fl
 static inline int head_pick_nt(int rows, bool split) {
     if (!split) return 1;
     return rows >= PC_SPLIT_NT4_MIN ? 4 : (rows >= PC_SPLIT_NT2_MIN ? 2 : 1);
+}
+// Host: f(PL, NT), both std::integral_constant<int, .>, for the trunk form pl and nt column tiles per workgroup.
+// A launch site instantiates the exact-fp32 form at 16-candidate tiles only, the f16x3 form at the widths up
+// to MAX_NT, and the hybrid form (at the same widths) only where Q8 says it can take it.
+template <int MAX_NT = 4, bool Q8 = false, typename F>
+static inline void head_dispatch(int pl, int nt, F f) {
+    auto widths = [&](auto PL) {
+        if constexpr (MAX_NT >= 4)
+            if (nt == 4) return f(PL, std::integral_constant<int, 4>{});
+        if constexpr (MAX_NT >= 2)
+            if (nt == 2) return f(PL, std::integral_constant<int, 2>{});
+        return f(PL, std::integral_constant<int, 1>{});
+    };
+    if (pl == 0) return f(std::integral_constant<int, 0>{}, std::integral_constant<int, 1>{});
+    if constexpr (Q8)
+        if (pl == X3Q) return widths(std::integral_constant<int, X3Q>{});
+    return widths(std::integral_constant<int, X3P>{});
 }
 
 // ============================================================================ pose helpers
@@ -1261,33 +1147,24 @@ __device__ __forceinline__ void gram_schmidt6(T* v) {
     v[5] = c2 / n2;
 }
 
-// Division / square root of the PC update chain: IEEE by default; PC_FAST_UPDATE builds use the
-// hardware v_rcp_f32 / v_sqrt_f32 (<= 1 ulp) to shorten wave 0's dependent chain (tuning only).
-#ifdef PC_FAST_UPDATE
-__device__ __forceinline__ float udiv(float a, float b) { return a * __builtin_amdgcn_rcpf(b); }
-__device__ __forceinline__ float usqrt(float x) { return __builtin_amdgcn_sqrtf(x); }
-#else
-__device__ __forceinline__ float udiv(float a, float b) { return fdiv(a, b); }
-__device__ __forceinline__ float usqrt(float x) { return sqrtf(x); }
-#endif
-
 // gram_schmidt6 spread over the four lanes of a row (lane part p: 0 -> v[0:3], 1 -> v[3:6],
-// 2 -> translation, untouched; 3 idle). Same operations and order as gram_schmidt6<float>.
+// 2 -> translation, untouched; 3 idle). Same operations and order as gram_schmidt6<float>: IEEE division
+// and square root on purpose (the hardware's approximate ones would not give the reference's bits).
 __device__ __forceinline__ void gram_schmidt6_quad(float* v, int p, int lane) {
 #pragma clang fp contract(off)
-    float n1 = usqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]);
+    float n1 = sqrtf((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]);
     n1 = n1 > 1e-12f ? n1 : 1e-12f;
-    const float b0 = udiv(v[0], n1), b1 = udiv(v[1], n1), b2 = udiv(v[2], n1);   // meaningful on p == 0
+    const float b0 = fdiv(v[0], n1), b1 = fdiv(v[1], n1), b2 = fdiv(v[2], n1);   // meaningful on p == 0
     (void)lane;
     const float B0 = quad_bcast0(b0), B1 = quad_bcast0(b1), B2 = quad_bcast0(b2);
     const float d = (B0 * v[0] + B1 * v[1]) + B2 * v[2];
     float c0 = v[0] - d * B0, c1 = v[1] - d * B1, c2 = v[2] - d * B2;
-    float n2 = usqrt((c0 * c0 + c1 * c1) + c2 * c2);
+    float n2 = sqrtf((c0 * c0 + c1 * c1) + c2 * c2);
     n2 = n2 > 1e-12f ? n2 : 1e-12f;
     if (p == 0) {
         v[0] = b0; v[1] = b1; v[2] = b2;
     } else if (p == 1) {
-        v[0] = udiv(c0, n2); v[1] = udiv(c1, n2); v[2] = udiv(c2, n2);
+        v[0] = fdiv(c0, n2); v[1] = fdiv(c1, n2); v[2] = fdiv(c2, n2);
     }
 }
 

@@ -68,6 +68,43 @@ struct OdeStageArgs {
     int stage;                   // 1..6
 };
 
+// The stage arithmetic the sampler's and the likelihood's stage kernels share, one definition each: a last-bit
+// difference in any of them can flip an accept / reject of the step controller.
+// y_in = y + (sum_{j<nk} a_j K_j) h of entry e, nk >= 1 (scipy rk.py rk_step's order)
+__device__ __forceinline__ double ode_stage_in(const double* const* kin, const double* acoef, int nk, double h, size_t e,
+                                               double yv) {
+#pragma clang fp contract(off)
+    double acc = kin[0][e] * acoef[0];
+    for (int s = 1; s < nk; ++s) acc = acc + kin[s][e] * acoef[s];
+    return yv + acc * h;
+}
+// scipy's error term of entry e: err = (K^T E) h / scale, scale = atol + max(|y|, |y_new|) rtol; kv = K_6[e], the
+// derivative this stage just formed
+__device__ __forceinline__ double ode_err_term(const OdeStageArgs& a, const double* const* kin, double kv, double h,
+                                               size_t e, double y0, double y1) {
+#pragma clang fp contract(off)
+    double acc = kin[0][e] * a.e[0];
+    for (int s = 1; s < ODE_NK - 1; ++s) acc = acc + kin[s][e] * a.e[s];
+    acc = acc + kv * a.e[ODE_NK - 1];
+    const double sc = a.atol + fmax(fabs(y0), fabs(y1)) * a.rtol;
+    return (acc * h) / sc;
+}
+// The workgroup's sum of the threads' sq in a fixed order (xor tree per wave, waves in order) -> *out; esq: one
+// double of LDS per wave
+__device__ __forceinline__ void ode_block_partial(double sq, double* esq, double* out) {
+#pragma clang fp contract(off)
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) sq += __shfl_xor(sq, off, 64);
+    if ((tid & 63) == 0) esq[tid >> 6] = sq;
+    __syncthreads();
+    if (tid == 0) {
+        double t = 0.0;
+        for (int v = 0; v < EVAL_WV; ++v) t += esq[v];
+        *out = t;
+    }
+}
+
 // One RK45 stage for the workgroup's rows. MODE 0: stage derivative. MODE 1: last stage of an attempt
 // (y_new, K_6, error partials). y_in = y + (sum_{j<nk} acoef_j K_j) h, K_out = coef * score(f32(y_in), t).
 template <int MODE, int PL, int NT>
@@ -78,24 +115,17 @@ __device__ __forceinline__ void ode_stage_body(const OdeStageArgs& a, const doub
                                                double* esq, const SplitScalars& hs) {
     constexpr int ROWS = 16 * NT;
     constexpr int NTH = EVAL_WV * 64;
-    constexpr bool SPLIT = PL != 0;
     const int tid = threadIdx.x;
     const int r0 = blockIdx.x * ROWS;
-    stage_small_weights<NT, EVAL_WV, 0, !SPLIT>(a.w, sm);
+    stage_small_weights(a.w, sm);
     for (int i = tid; i < ROWS * 16; i += NTH) {
         const int c = i >> 4, j = i & 15;
         const int r = r0 + c;
         float xv = 0.f;
         if (r < a.rows && j < 9) {
-#pragma clang fp contract(off)
             const size_t e = (size_t)r * 9 + j;
             const double yv = y[e];
-            double yi = yv;
-            if (nk > 0) {
-                double acc = kin[0][e] * acoef[0];
-                for (int s = 1; s < nk; ++s) acc = acc + kin[s][e] * acoef[s];
-                yi = yv + acc * h;
-            }
+            const double yi = nk > 0 ? ode_stage_in(kin, acoef, nk, h, e, yv) : yv;
             xv = (float)yi;   // torch.tensor(x, dtype=torch.float32) (samplers.py:210)
             if (MODE == 1) {
                 y0s[c * 9 + j] = yv;
@@ -105,14 +135,8 @@ __device__ __forceinline__ void ode_stage_body(const OdeStageArgs& a, const doub
         }
         sm.xin[i] = xv;
     }
-    if (tid < ROWS) {
-        const int r = r0 + tid;
-        obj[tid] = (r < a.rows ? r : a.rows - 1) / a.kper;
-    }
-    if constexpr (SPLIT)
-        head_trunk_x3<NT, EVAL_WV>(a.w, a.pobj, tproj, obj, sm, 0, hs);
-    else
-        head_trunk<NT, EVAL_WV>(a.w, a.pobj, tproj, obj, sm);
+    if (tid < ROWS) obj[tid] = obj_of_row(r0 + tid, a.rows, a.kper);
+    run_head_trunk(a.w, a.pobj, tproj, obj, sm, 0, hs);
     double sq = 0.0;   // this thread's (err/scale)^2 terms, its elements in increasing order
     for (int e9 = tid; e9 < ROWS * 9; e9 += NTH) {
 #pragma clang fp contract(off)
@@ -124,29 +148,12 @@ __device__ __forceinline__ void ode_stage_body(const OdeStageArgs& a, const doub
             const double kv = coef * (double)s;
             kout[e] = kv;
             if (MODE == 1) {
-                // scipy: err = (K^T E) * h / scale, scale = atol + max(|y|, |y_new|) * rtol
-                double acc = kin[0][e] * a.e[0];
-                for (int s2 = 1; s2 < ODE_NK - 1; ++s2) acc = acc + kin[s2][e] * a.e[s2];
-                acc = acc + kv * a.e[ODE_NK - 1];
-                const double y0 = y0s[c * 9 + o], y1 = y1s[c * 9 + o];
-                const double sc = a.atol + fmax(fabs(y0), fabs(y1)) * a.rtol;
-                const double er = (acc * h) / sc;
+                const double er = ode_err_term(a, kin, kv, h, e, y0s[c * 9 + o], y1s[c * 9 + o]);
                 sq += er * er;
             }
         }
     }
-    if (MODE == 1) {
-        // workgroup partial in a fixed order: per-thread sums, xor tree per wave, waves in order
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) sq += __shfl_xor(sq, off, 64);
-        if ((tid & 63) == 0) esq[tid >> 6] = sq;
-        __syncthreads();
-        if (tid == 0) {
-            double t = 0.0;
-            for (int v = 0; v < EVAL_WV; ++v) t += esq[v];
-            a.part[a.part_off + blockIdx.x] = t;
-        }
-    }
+    if (MODE == 1) ode_block_partial(sq, esq, &a.part[a.part_off + blockIdx.x]);
 }
 
 // MODE 0: stage derivative. MODE 1: last stage of an attempt (y_new, K_6, error partials).
@@ -157,11 +164,9 @@ __global__ __launch_bounds__(EVAL_WV * 64) void ode_stage_kernel(OdeStageArgs a)
     constexpr int ROWS = 16 * NT;
     constexpr int NTH = EVAL_WV * 64;
     __shared__ HeadSmem<NT, EVAL_WV, PL> sm;
-    constexpr bool SPLIT = PL != 0;
     __shared__ int obj[ROWS];
     __shared__ double y0s[ROWS * 9], y1s[ROWS * 9], esq[NTH];
-    SplitScalars hs = {};
-    if constexpr (SPLIT) hs = load_split_scalars(a.w);
+    const SplitScalars hs = load_split_scalars<PL>(a.w);
     const double* y = a.y;
     const double* kin[ODE_NK];
 #pragma unroll
@@ -202,7 +207,6 @@ __global__ __launch_bounds__(EVAL_WV * 64) void ode_attempt_kernel(OdeStageArgs 
     constexpr int ROWS = 16 * NT;
     constexpr int NTH = EVAL_WV * 64;
     __shared__ HeadSmem<NT, EVAL_WV, PL> sm;
-    constexpr bool SPLIT = PL != 0;
     __shared__ int obj[ROWS];
     __shared__ double y0s[ROWS * 9], y1s[ROWS * 9], esq[NTH];
     // the tableau and the K slots of this attempt in LDS: read per use (wave-uniform), not held in registers
@@ -221,15 +225,13 @@ __global__ __launch_bounds__(EVAL_WV * 64) void ode_attempt_kernel(OdeStageArgs 
     for (int s = 1; s < 6; ++s) {
         if (s > 1) __syncthreads();   // stage s-1's K stores and its reads of the staged weights are done
         // per stage (L2-resident): held across the stages they would add to the trunk's register peak
-        SplitScalars hs = {};
-        if constexpr (SPLIT) hs = load_split_scalars(a.w);
+        const SplitScalars hs = load_split_scalars<PL>(a.w);
         ode_stage_body<0, PL, NT>(a, y, kin, tab + s * 6, s, h, c->coef[s - 1], c->sig[s - 1],
                                   a.tproj6 + (size_t)(s - 1) * 768, const_cast<double*>(kin[s]), nullptr, sm, obj,
                                   y0s, y1s, esq, hs);
     }
     __syncthreads();
-    SplitScalars hs = {};
-    if constexpr (SPLIT) hs = load_split_scalars(a.w);
+    const SplitScalars hs = load_split_scalars<PL>(a.w);
     ode_stage_body<1, PL, NT>(a, y, kin, tab + 36, 6, h, c->coef[5], c->sig[5], a.tproj6 + (size_t)5 * 768,
                               const_cast<double*>(kin[6]), a.ybuf[c->yi ^ 1], sm, obj, y0s, y1s, esq, hs);
 }
@@ -239,14 +241,9 @@ template <int MODE>
 static void ode_launch_stage(const OdeStageArgs& a, int nt, hipStream_t st) {
     const int nwg = (a.rows + 16 * nt - 1) / (16 * nt);
     const dim3 grid(nwg), blk(EVAL_WV * 64);
-    if (!a.w.pe2_h)
-        hipLaunchKernelGGL((ode_stage_kernel<MODE, 0, 1>), grid, blk, 0, st, a);
-    else if (nt == 4)
-        hipLaunchKernelGGL((ode_stage_kernel<MODE, X3P, 4>), grid, blk, 0, st, a);
-    else if (nt == 2)
-        hipLaunchKernelGGL((ode_stage_kernel<MODE, X3P, 2>), grid, blk, 0, st, a);
-    else
-        hipLaunchKernelGGL((ode_stage_kernel<MODE, X3P, 1>), grid, blk, 0, st, a);
+    head_dispatch(a.w.pe2_h ? X3P : 0, nt, [&](auto pl, auto ntc) {
+        hipLaunchKernelGGL((ode_stage_kernel<MODE, pl.value, ntc.value>), grid, blk, 0, st, a);
+    });
 }
 
 static int ode_nt(const gp_head_weights* w, int rows) { return head_pick_nt(rows, w->pe2_h != nullptr); }
@@ -266,28 +263,16 @@ __global__ __launch_bounds__(EVAL_WV * 64) void like_stage_kernel(OdeStageArgs a
     constexpr int NT = 2 * NP;
     constexpr int ROWS = 16 * NP;     // rows (candidates) of this workgroup
     constexpr int NTH = EVAL_WV * 64;
-    constexpr bool SPLIT = PL != 0;
     __shared__ HeadSmem<NT, EVAL_WV, PL> sm;
     __shared__ int obj[2 * ROWS];
     __shared__ double y0s[ROWS * 10], y1s[ROWS * 10], esq[EVAL_WV];
-    SplitScalars hs = {};
-    if constexpr (SPLIT) hs = load_split_scalars(a.w);
+    const SplitScalars hs = load_split_scalars<PL>(a.w);
     const int tid = threadIdx.x;
     const int r0 = blockIdx.x * ROWS;
     const double h = a.h;
     const size_t n9 = (size_t)a.rows * 9;
-    stage_small_weights<NT, EVAL_WV, 0, !SPLIT>(a.w, sm);
-    // y_in = y + (sum_{j<nk} a_j K_j) h of entry e (ode_stage_body's expression)
-    auto stage_in = [&](size_t e, double yv) {
-#pragma clang fp contract(off)
-        double yi = yv;
-        if (a.nk > 0) {
-            double acc = a.k[0][e] * a.a[0];
-            for (int s = 1; s < a.nk; ++s) acc = acc + a.k[s][e] * a.a[s];
-            yi = yv + acc * h;
-        }
-        return yi;
-    };
+    stage_small_weights(a.w, sm);
+    auto stage_in = [&](size_t e, double yv) { return a.nk > 0 ? ode_stage_in(a.k, a.a, a.nk, h, e, yv) : yv; };
     for (int i = tid; i < 2 * ROWS * 16; i += NTH) {
         const int c = i >> 4, j = i & 15;
         float xv = 0.f;
@@ -318,11 +303,8 @@ __global__ __launch_bounds__(EVAL_WV * 64) void like_stage_kernel(OdeStageArgs a
         y1s[tid * 10 + 9] = yi;
         a.ynew[e] = yi;
     }
-    if (tid < 2 * ROWS) {
-        const int r = r0 + (tid < ROWS ? tid : tid - ROWS);
-        obj[tid] = (r < a.rows ? r : a.rows - 1) / a.kper;
-    }
-    if constexpr (SPLIT)
+    if (tid < 2 * ROWS) obj[tid] = obj_of_row(r0 + (tid < ROWS ? tid : tid - ROWS), a.rows, a.kper);
+    if constexpr (PL != 0)
         head_trunk_x3<NT, EVAL_WV, false, true>(a.w, a.pobj, a.tproj, obj, sm, 0, hs);
     else
         head_trunk<NT, EVAL_WV, true>(a.w, a.pobj, a.tproj, obj, sm);
@@ -341,32 +323,18 @@ __global__ __launch_bounds__(EVAL_WV * 64) void like_stage_kernel(OdeStageArgs a
                 s = 0.f;
 #pragma unroll
                 for (int j = 0; j < 9; ++j)
-                    s = fadd(s, fmul(ld1(&sm.xin[(ROWS + c) * 16 + j]), fdiv(head_out_tan(sm, ROWS + c, j), den)));
+                    s = fadd(s, fmul(ld1(&sm.xin[(ROWS + c) * 16 + j]), fdiv(head_out<true>(sm, ROWS + c, j), den)));
             }
             const double kv = a.coef * (double)s;
             a.kout[e] = kv;
             if (MODE == 1) {
-                double acc = a.k[0][e] * a.e[0];
-                for (int s2 = 1; s2 < ODE_NK - 1; ++s2) acc = acc + a.k[s2][e] * a.e[s2];
-                acc = acc + kv * a.e[ODE_NK - 1];
-                const double y0 = y0s[e10], y1 = y1s[e10];
-                const double sc = a.atol + fmax(fabs(y0), fabs(y1)) * a.rtol;
-                const double er = (acc * h) / sc;
+                const double er = ode_err_term(a, a.k, kv, h, e, y0s[e10], y1s[e10]);
                 sq += er * er;
             }
         }
     }
-    if (MODE == 1) {
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) sq += __shfl_xor(sq, off, 64);
-        if ((tid & 63) == 0) esq[tid >> 6] = sq;
-        __syncthreads();
-        if (tid == 0) {
-            double t = 0.0;
-            for (int v = 0; v < EVAL_WV; ++v) t += esq[v];
-            a.part[blockIdx.x] = t;
-        }
-    }
+    // part_off stays out of it: the likelihood has no global-batch shards (host-side it is always 0 here)
+    if (MODE == 1) ode_block_partial(sq, esq, &a.part[blockIdx.x]);
 }
 
 // Primal column tiles per workgroup of the likelihood stages: a workgroup streams the GEMM weights once for its
@@ -379,12 +347,9 @@ static int like_np(const gp_head_weights* w, int rows) {
 template <int MODE>
 static void like_launch_stage(const OdeStageArgs& a, const float* eps, int np, hipStream_t st) {
     const dim3 grid((a.rows + 16 * np - 1) / (16 * np)), blk(EVAL_WV * 64);
-    if (!a.w.pe2_h)
-        hipLaunchKernelGGL((like_stage_kernel<MODE, 0, 1>), grid, blk, 0, st, a, eps);
-    else if (np == 2)
-        hipLaunchKernelGGL((like_stage_kernel<MODE, X3P, 2>), grid, blk, 0, st, a, eps);
-    else
-        hipLaunchKernelGGL((like_stage_kernel<MODE, X3P, 1>), grid, blk, 0, st, a, eps);
+    head_dispatch<2>(a.w.pe2_h ? X3P : 0, np, [&](auto pl, auto npc) {
+        hipLaunchKernelGGL((like_stage_kernel<MODE, pl.value, npc.value>), grid, blk, 0, st, a, eps);
+    });
 }
 
 // Sum of part[0..n) by a 256-thread workgroup in a fixed order (strided per-thread sums, xor
@@ -550,22 +515,15 @@ __global__ __launch_bounds__(EVAL_WV * 64) void ode_denoise_kernel(OdeDenoiseArg
     __shared__ double xm[ROWS * 9];
     const int tid = threadIdx.x;
     const int r0 = blockIdx.x * ROWS;
-    SplitScalars hs = {};
-    if constexpr (PL != 0) hs = load_split_scalars(a.w);
-    stage_small_weights<NT, EVAL_WV, 0, PL == 0>(a.w, sm);
+    const SplitScalars hs = load_split_scalars<PL>(a.w);
+    stage_small_weights(a.w, sm);
     for (int i = tid; i < ROWS * 16; i += NTH) {
         const int c = i >> 4, j = i & 15;
         const int r = r0 + c;
         sm.xin[i] = (r < a.rows && j < 9) ? (float)a.x[(size_t)r * 9 + j] : 0.f;
     }
-    if (tid < ROWS) {
-        const int r = r0 + tid;
-        obj[tid] = (r < a.rows ? r : a.rows - 1) / a.kper;
-    }
-    if constexpr (PL != 0)
-        head_trunk_x3<NT, EVAL_WV>(a.w, a.pobj, a.tproj, obj, sm, 0, hs);
-    else
-        head_trunk<NT, EVAL_WV>(a.w, a.pobj, a.tproj, obj, sm);
+    if (tid < ROWS) obj[tid] = obj_of_row(r0 + tid, a.rows, a.kper);
+    run_head_trunk(a.w, a.pobj, a.tproj, obj, sm, 0, hs);
     for (int e9 = tid; e9 < ROWS * 9; e9 += NTH) {
 #pragma clang fp contract(off)
         const int c = e9 / 9, o = e9 - c * 9;
@@ -846,14 +804,9 @@ extern "C" int gp_ode_denoise(const gp_head_weights* w, const float* pobj, float
     // the stage kernels' trunk and tile (exact fp32 without the f16 planes)
     const int nt = ode_nt(w, rows);
     const dim3 grid((rows + 16 * nt - 1) / (16 * nt)), blk(EVAL_WV * 64);
-    if (!w->pe2_h)
-        hipLaunchKernelGGL((ode_denoise_kernel<0, 1>), grid, blk, 0, stream, a);
-    else if (nt == 4)
-        hipLaunchKernelGGL((ode_denoise_kernel<X3P, 4>), grid, blk, 0, stream, a);
-    else if (nt == 2)
-        hipLaunchKernelGGL((ode_denoise_kernel<X3P, 2>), grid, blk, 0, stream, a);
-    else
-        hipLaunchKernelGGL((ode_denoise_kernel<X3P, 1>), grid, blk, 0, stream, a);
+    head_dispatch(w->pe2_h ? X3P : 0, nt, [&](auto pl, auto ntc) {
+        hipLaunchKernelGGL((ode_denoise_kernel<pl.value, ntc.value>), grid, blk, 0, stream, a);
+    });
     return gp_check_launch("ode_denoise_kernel");
 }
 
@@ -1045,14 +998,9 @@ static int ode_auto_attempt_impl(const gp_head_weights* w, const float* pobj, in
         for (int j = 0; j < ODE_NK; ++j) a.e[j] = e[j];
         a.part = part;
         const dim3 grid(nwg), blk(EVAL_WV * 64);
-        if (!w->pe2_h)
-            hipLaunchKernelGGL((ode_attempt_kernel<0, 1>), grid, blk, 0, stream, a, tb);
-        else if (nt == 4)
-            hipLaunchKernelGGL((ode_attempt_kernel<X3P, 4>), grid, blk, 0, stream, a, tb);
-        else if (nt == 2)
-            hipLaunchKernelGGL((ode_attempt_kernel<X3P, 2>), grid, blk, 0, stream, a, tb);
-        else
-            hipLaunchKernelGGL((ode_attempt_kernel<X3P, 1>), grid, blk, 0, stream, a, tb);
+        head_dispatch(w->pe2_h ? X3P : 0, nt, [&](auto pl, auto ntc) {
+            hipLaunchKernelGGL((ode_attempt_kernel<pl.value, ntc.value>), grid, blk, 0, stream, a, tb);
+        });
         const int rc = gp_check_launch("ode_attempt_kernel");
         if (rc || !g) return rc;
         GP_REQUIRE(g->exchange(g->ctx, n, part, part_n, stream) == 0, "ode_auto_attempt: partials exchange of attempt %d",

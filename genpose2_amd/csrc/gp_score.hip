@@ -91,28 +91,32 @@ extern "C" int gp_head_time_proj(const gp_head_weights* w, const float* t, int n
 }
 
 // ============================================================================ score / energy eval
+// The evaluation kernels' input: column c < 16 of xin is row r0 + c of x (nine of sixteen entries, zeros past
+// `rows`) and, for a JVP trunk's two tiles, column 16 + c the same row of eps.
+template <int NT, int WV, int PL>
+__device__ __forceinline__ void load_rows_xin(HeadSmem<NT, WV, PL>& sm, const float* x, const float* eps, int r0,
+                                              int rows) {
+    static_assert(NT <= 2, "one primal tile, with its tangent tile or without");
+    for (int i = threadIdx.x; i < NT * 256; i += WV * 64) {
+        const int c = i >> 4, j = i & 15;
+        const int r = r0 + (NT > 1 ? c & 15 : c);
+        const float* src = NT == 1 || c < 16 ? x : eps;
+        sm.xin[i] = (r < rows && j < 9) ? src[(size_t)r * 9 + j] : 0.f;
+    }
+}
 template <int MODE, int PL>  // MODE 0: score f/(sigma+1e-7), 1: energy (IP, decoupled); PL 0: exact fp32, X3P: f16x3
 __global__ __launch_bounds__(EVAL_WV * 64) void head_eval_kernel(gp_head_weights w, const float* __restrict__ pobj,
                                                        const float* __restrict__ tproj, float sigma,
                                                        const float* __restrict__ x, int rows, int kper,
                                                        float* __restrict__ out) {
     __shared__ HeadSmem<1, EVAL_WV, PL> sm;
-    constexpr bool SPLIT = PL != 0;
     __shared__ int obj[16];
     const int r0 = blockIdx.x * 16;
-    SplitScalars hs = {};
-    if constexpr (SPLIT) hs = load_split_scalars(w);
-    stage_small_weights<1, EVAL_WV, 0, !SPLIT>(w, sm);
-    for (int i = threadIdx.x; i < 256; i += EVAL_WV * 64) {
-        const int c = i >> 4, j = i & 15;
-        const int r = r0 + c;
-        sm.xin[i] = (r < rows && j < 9) ? x[(size_t)r * 9 + j] : 0.f;
-    }
-    if (threadIdx.x < 16) {
-        const int r = r0 + threadIdx.x;
-        obj[threadIdx.x] = (r < rows ? r : rows - 1) / kper;
-    }
-    if constexpr (SPLIT)
+    const SplitScalars hs = load_split_scalars<PL>(w);
+    stage_small_weights(w, sm);
+    load_rows_xin(sm, x, nullptr, r0, rows);
+    if (threadIdx.x < 16) obj[threadIdx.x] = obj_of_row(r0 + threadIdx.x, rows, kper);
+    if constexpr (PL != 0)
         head_trunk_x3<1, EVAL_WV>(w, pobj, tproj, obj, sm, 0, hs);
     else
         head_trunk<1, EVAL_WV>(w, pobj, tproj, obj, sm);
@@ -146,16 +150,12 @@ extern "C" int gp_score_eval(const gp_head_weights* w, const float* pobj, const 
     GP_REQUIRE(w && pobj && tproj_row && x && score && rows >= 0 && k >= 1, "score_eval: bad arguments");
     if (!rows) return GP_OK;
     // the trunk gp_pc_sample runs on this many rows: the hybrid form where it takes it
-    if (w->pe2_h && (w->q8_flags & GP_Q8_EVAL) && w->pe2_q && w->h1p_q &&
-        ((w->q8_flags & GP_Q8_ALL_TILES) || head_pick_nt(rows, true) == 4))
-        hipLaunchKernelGGL((head_eval_kernel<0, X3Q>), dim3((rows + 15) / 16), dim3(EVAL_WV * 64), 0, stream, *w, pobj, tproj_row,
-                       sigma, x, rows, k, score);
-    else if (w->pe2_h)
-        hipLaunchKernelGGL((head_eval_kernel<0, X3P>), dim3((rows + 15) / 16), dim3(EVAL_WV * 64), 0, stream, *w, pobj, tproj_row,
-                       sigma, x, rows, k, score);
-    else
-        hipLaunchKernelGGL((head_eval_kernel<0, 0>), dim3((rows + 15) / 16), dim3(EVAL_WV * 64), 0, stream, *w, pobj, tproj_row,
-                       sigma, x, rows, k, score);
+    const bool q8 = w->pe2_h && (w->q8_flags & GP_Q8_EVAL) && w->pe2_q && w->h1p_q &&
+                    ((w->q8_flags & GP_Q8_ALL_TILES) || head_pick_nt(rows, true) == 4);
+    head_dispatch<1, true>(q8 ? X3Q : (w->pe2_h ? X3P : 0), 1, [&](auto pl, auto) {
+        hipLaunchKernelGGL((head_eval_kernel<0, pl.value>), dim3((rows + 15) / 16), dim3(EVAL_WV * 64), 0, stream, *w, pobj,
+                           tproj_row, sigma, x, rows, k, score);
+    });
     return gp_check_launch("head_eval_kernel<score>");
 }
 
@@ -169,23 +169,13 @@ __global__ __launch_bounds__(EVAL_WV * 64) void head_div_eval_kernel(gp_head_wei
                                                        int rows, int kper, float* __restrict__ score,
                                                        float* __restrict__ div) {
     __shared__ HeadSmem<2, EVAL_WV, PL> sm;
-    constexpr bool SPLIT = PL != 0;
     __shared__ int obj[32];
     const int r0 = blockIdx.x * 16;
-    SplitScalars hs = {};
-    if constexpr (SPLIT) hs = load_split_scalars(w);
-    stage_small_weights<2, EVAL_WV, 0, !SPLIT>(w, sm);
-    for (int i = threadIdx.x; i < 512; i += EVAL_WV * 64) {
-        const int c = i >> 4, j = i & 15;
-        const int r = r0 + (c & 15);
-        const float* src = c < 16 ? x : eps;
-        sm.xin[i] = (r < rows && j < 9) ? src[(size_t)r * 9 + j] : 0.f;
-    }
-    if (threadIdx.x < 32) {
-        const int r = r0 + (threadIdx.x & 15);
-        obj[threadIdx.x] = (r < rows ? r : rows - 1) / kper;
-    }
-    if constexpr (SPLIT)
+    const SplitScalars hs = load_split_scalars<PL>(w);
+    stage_small_weights(w, sm);
+    load_rows_xin(sm, x, eps, r0, rows);
+    if (threadIdx.x < 32) obj[threadIdx.x] = obj_of_row(r0 + (threadIdx.x & 15), rows, kper);
+    if constexpr (PL != 0)
         head_trunk_x3<2, EVAL_WV, false, true>(w, pobj, tproj, obj, sm, 0, hs);
     else
         head_trunk<2, EVAL_WV, true>(w, pobj, tproj, obj, sm);
@@ -198,7 +188,7 @@ __global__ __launch_bounds__(EVAL_WV * 64) void head_div_eval_kernel(gp_head_wei
             } else {
                 float d = 0.f;
 #pragma unroll
-                for (int j = 0; j < 9; ++j) d = fadd(d, fmul(ld1(&sm.xin[(16 + c) * 16 + j]), fdiv(head_out_tan(sm, 16 + c, j), den)));
+                for (int j = 0; j < 9; ++j) d = fadd(d, fmul(ld1(&sm.xin[(16 + c) * 16 + j]), fdiv(head_out<true>(sm, 16 + c, j), den)));
                 div[r0 + c] = d;
             }
         }
@@ -246,16 +236,9 @@ __global__ __launch_bounds__(EVAL_WV * 64) void head_grad_eval_kernel(gp_head_we
     __shared__ GradSmem gs;
     __shared__ int obj[16];
     const int r0 = blockIdx.x * 16;
-    stage_small_weights<1, EVAL_WV, 0, true>(w, sm);
-    for (int i = threadIdx.x; i < 256; i += EVAL_WV * 64) {
-        const int c = i >> 4, j = i & 15;
-        const int r = r0 + c;
-        sm.xin[i] = (r < rows && j < 9) ? x[(size_t)r * 9 + j] : 0.f;
-    }
-    if (threadIdx.x < 16) {
-        const int r = r0 + threadIdx.x;
-        obj[threadIdx.x] = (r < rows ? r : rows - 1) / kper;
-    }
+    stage_small_weights(w, sm);
+    load_rows_xin(sm, x, nullptr, r0, rows);
+    if (threadIdx.x < 16) obj[threadIdx.x] = obj_of_row(r0 + threadIdx.x, rows, kper);
     head_trunk<1, EVAL_WV, false, true>(w, pobj, tproj, obj, sm, 0, &gs, sigma);
     head_backward<EVAL_WV>(gw, sm, gs);
     // a lane per (row, output); the products x_o f_o / sigma of the energy go through LDS to the row's first lane.
@@ -342,7 +325,7 @@ __device__ __forceinline__ void pc_update_rows(const PCArgs& a, int i, const PCS
                                                int* obj, int g, int lane, int r0, float gacc, float (&x3)[3],
                                                const float (&sv)[3], const float (&z1v)[3], const float (&z2v)[3],
                                                const SplitScalars& hs, bool store_x, int trace_slot) {
-#pragma clang fp contract(off)
+#pragma clang fp contract(off)   // and IEEE division / square root on purpose: the chain gives the reference's bits
     constexpr bool SPLIT = PL != 0;
     const int p = lane & 3;
     const int e0 = 3 * (p < 3 ? p : 0);
@@ -357,16 +340,16 @@ __device__ __forceinline__ void pc_update_rows(const PCArgs& a, int i, const PCS
     const int r = r0 + c;
     const bool upd = i > 0 && r < a.rows && p < 3;
     if (upd) {
-        const float gn = udiv(gacc, (float)a.norm_rows);
-        const float ratio = udiv(a.ls_coef, gn);
+        const float gn = fdiv(gacc, (float)a.norm_rows);
+        const float ratio = fdiv(a.ls_coef, gn);
         const float ls = 2.0f * (ratio * ratio);
-        const float sq2ls = usqrt(2.0f * ls);
+        const float sq2ls = sqrtf(2.0f * ls);
         float mean[3];
 #pragma unroll
         for (int k = 0; k < 3; ++k) x3[k] = (x3[k] + ls * sv[k]) + sq2ls * z1v[k];
         if (p < 2) {   // x[:, :3] /= ||x[:, :3]||, x[:, 3:6] /= ||x[:, 3:6]|| (samplers.py:157-160)
-            const float nn = usqrt((x3[0] * x3[0] + x3[1] * x3[1]) + x3[2] * x3[2]);
-            x3[0] = udiv(x3[0], nn); x3[1] = udiv(x3[1], nn); x3[2] = udiv(x3[2], nn);
+            const float nn = sqrtf((x3[0] * x3[0] + x3[1] * x3[1]) + x3[2] * x3[2]);
+            x3[0] = fdiv(x3[0], nn); x3[1] = fdiv(x3[1], nn); x3[2] = fdiv(x3[2], nn);
         }
         // reverse-SDE Euler-Maruyama predictor (samplers.py:163-166; sign as in the reference)
         const float g2 = prev.g * prev.g;
@@ -537,15 +520,13 @@ __global__ __launch_bounds__(WV * 64) void pc_step_kernel(std::conditional_t<GRA
     static_assert(NT < WV, "at least one wave besides the update waves");
     static_assert(!GRAD || (NT == 1 && PL == 0), "the energy gradient runs the exact-fp32 16-candidate tile");
     __shared__ HeadSmem<NT, WV, PL> sm;
-    constexpr bool SPLIT = PL != 0;
     __shared__ int obj[ROWS];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r0 = blockIdx.x * ROWS;
     const int trace_slot = i == a.steps ? 2 : (i & 1);
-    SplitScalars hs = {};
-    if constexpr (SPLIT) hs = load_split_scalars<WV>(a.w);   // in flight across the update
+    const SplitScalars hs = load_split_scalars<PL, WV>(a.w);   // in flight across the update
     PC_MARK(0);
     if (wid < NT) {
         // ---- every load first and unconditional (rows clamped: a guarded load becomes a branch,
@@ -592,7 +573,7 @@ __global__ __launch_bounds__(WV * 64) void pc_step_kernel(std::conditional_t<GRA
         pc_make_draws<NT, WV>(a, i, r0, [&](int st, int c, int e, float v) {
             a.zbuf[((size_t)((i & 1) * 2 + st) * a.rows + r0 + c) * 9 + e] = v;
         });
-    stage_small_weights<NT, WV, 64 * NT, !SPLIT>(a.w, sm);
+    stage_small_weights<64 * NT>(a.w, sm);
     if constexpr (GRAD) {
         __shared__ GradSmem gs;
         head_trunk<NT, WV, false, true>(a.w, a.pobj, a.tproj + (size_t)i * 768, obj, sm, trace_slot, &gs, cur.sigma);
@@ -603,10 +584,7 @@ __global__ __launch_bounds__(WV * 64) void pc_step_kernel(std::conditional_t<GRA
         if (tid == 0) a.part[(size_t)(i & 1) * a.part_n + a.part_off + blockIdx.x] = t;
         PC_MARK(8);
     } else {
-        if constexpr (SPLIT)
-            head_trunk_x3<NT, WV, true>(a.w, a.pobj, a.tproj + (size_t)i * 768, obj, sm, trace_slot, hs);
-        else
-            head_trunk<NT, WV>(a.w, a.pobj, a.tproj + (size_t)i * 768, obj, sm, trace_slot);
+        run_head_trunk<true>(a.w, a.pobj, a.tproj + (size_t)i * 768, obj, sm, trace_slot, hs);
         PC_MARK(7);
         const float t = pc_score_norm<NT, WV, PL>(a, cur, sm, r0, wid, lane,
                                                   [&](int c, int o, float v) { a.s[(size_t)(r0 + c) * 9 + o] = v; });
@@ -740,20 +718,11 @@ static int pc_sample_impl(const gp_head_weights* w, const float* pobj, const flo
             ag.gw = *gw;
             hipLaunchKernelGGL((pc_step_kernel<1, PC_WV1, 0, true>), grid, dim3(PC_WV1 * 64), 0, stream, ag, i, cur, prev);
         }
-        else if (q8 && nt == 4)
-            hipLaunchKernelGGL((pc_step_kernel<4, PC_WV1, X3Q>), grid, dim3(PC_WV1 * 64), 0, stream, a, i, cur, prev);
-        else if (q8 && nt == 2)
-            hipLaunchKernelGGL((pc_step_kernel<2, PC_WV1, X3Q>), grid, dim3(PC_WV1 * 64), 0, stream, a, i, cur, prev);
-        else if (q8)
-            hipLaunchKernelGGL((pc_step_kernel<1, PC_WV1, X3Q>), grid, dim3(PC_WV1 * 64), 0, stream, a, i, cur, prev);
-        else if (nt == 4)
-            hipLaunchKernelGGL((pc_step_kernel<4, PC_WV1, X3P>), grid, dim3(PC_WV1 * 64), 0, stream, a, i, cur, prev);
-        else if (nt == 2)
-            hipLaunchKernelGGL((pc_step_kernel<2, PC_WV1, X3P>), grid, dim3(PC_WV1 * 64), 0, stream, a, i, cur, prev);
-        else if (split)
-            hipLaunchKernelGGL((pc_step_kernel<1, PC_WV1, X3P>), grid, dim3(PC_WV1 * 64), 0, stream, a, i, cur, prev);
         else
-            hipLaunchKernelGGL((pc_step_kernel<1, PC_WV1, 0>), grid, dim3(PC_WV1 * 64), 0, stream, a, i, cur, prev);
+            head_dispatch<4, true>(q8 ? X3Q : (split ? X3P : 0), nt, [&](auto pl, auto ntc) {
+                hipLaunchKernelGGL((pc_step_kernel<ntc.value, PC_WV1, pl.value>), grid, dim3(PC_WV1 * 64), 0, stream, a, i, cur,
+                                   prev);
+            });
         if (exchange != nullptr && i < steps) {   // launch i's partials -> every shard before launch i + 1 reads them
             const int rc = gp_check_launch("pc_step_kernel");
             if (rc) return rc;

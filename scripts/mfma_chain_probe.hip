@@ -13,7 +13,7 @@
 //   pattern 7: as 5 over two chunks at once (ten correction products per chain, two main per chain)
 //   pattern 10: as 1 with the B operands of the next column tile made by 12 VALU ops (v_xor) per 12 MFMAs
 //   pattern 11: as 1 with the B operands of the next column tile read from LDS (3 ds_read_b128 per
-//              12 MFMAs, one column tile ahead, as the kernel's X3_BPIPE)
+//              12 MFMAs, one column tile ahead, as the kernel's stream_x3_rec)
 //   pattern 8 / 9: v_mfma_f32_16x16x4_f32, 8 per 32-deep chunk: two tiles alternating / each tile's 8
 //              back to back (the exact-fp32 trunk)
 // Usage: mfma_chain_probe [ITERS [FILL [WGS]]] (FILL: operand bits, see main; WGS workgroups, 64 default).

@@ -131,15 +131,14 @@ class _Like:
         return kout
 
 
-@pytest.mark.parametrize("arith", ("f16x3", "f32"))
-def test_like_attempt_equals_six_rhs_calls(agent, arith):
-    """gp_like_attempt at R = 10 against the same step built from six gp_like_rhs calls: the same K_1..K_6 and
+def _attempt_vs_six_rhs(agent, arith, R, K, seed):
+    """gp_like_attempt at R rows against the same step built from six gp_like_rhs calls: the same K_1..K_6 and
     y_new bits, and an error norm within 1e-12 relative of scipy's expression in float64 NumPy over the downloaded
     stages (all 10 R entries under one RMS norm)."""
     from genpose2_amd import ode
     agent.heads.set_arith(arith)
     try:
-        L = _Like(agent, 10, 5, 17)
+        L = _Like(agent, R, K, seed)
         t, h, rtol, atol = 0.3, 2e-3, 1e-5, 1e-5
         K0 = L.rhs(t)
         # stage by stage
@@ -179,6 +178,19 @@ def test_like_attempt_equals_six_rhs_calls(agent, arith):
         assert e.size == 10 * L.R and abs(got - norm) <= 1e-12 * norm
     finally:
         agent.heads.set_arith("f16x3")
+
+
+@pytest.mark.parametrize("arith", ("f16x3", "f32"))
+def test_like_attempt_equals_six_rhs_calls(agent, arith):
+    """_attempt_vs_six_rhs at R = 10."""
+    _attempt_vs_six_rhs(agent, arith, 10, 5, 17)
+
+
+def test_like_attempt_equals_six_rhs_calls_two_primal_tiles(agent):
+    """_attempt_vs_six_rhs at R = 4,097, the smallest row count at which the f16x3 likelihood stages take two
+    primal tiles per workgroup (the attempt's last stage with y_new and the error partials included; its last
+    workgroup holds one row)."""
+    _attempt_vs_six_rhs(agent, "f16x3", 4097, 1, 29)
 
 
 def test_like_rhs_tilings_agree_bitwise(agent):
