@@ -596,8 +596,8 @@ constexpr int X3P = 3;           // planes per operand
 // MFMAs, 288 cycles against 384.
 // An e4m3 plane is the f16 plane times a constant power of two that brings the plane's bound to 2^7..2^8
 // (hi < 2^15 -> x 2^-7, |mid| <= 2^3 -> x 2^4, |lo| <= 2^-9 -> x 2^16; e4m3's largest value is 448), converted
-// with v_cvt_pk_fp8_f32 (round to nearest even, subnormals kept). The instruction's E8M0 block scales, constants,
-// undo the two planes' constants, so the products enter `cor` in the scaled domain of the f16 ones.
+// with v_cvt_scalef32_pk_fp8_f16 (q8_of: round to nearest even, subnormals kept). The MFMA's E8M0 block scales,
+// constants, undo the two planes' constants, so the products enter `cor` in the scaled domain of the f16 ones.
 // Product k of a group is issued with chunk 4g + k of the f16 stream (k < 3), its A planes riding in that chunk's
 // ring slot. Lane (q, i) of an operand holds 32 bytes per group: byte 8 cc + j is element j of the lane's f16
 // fragment of chunk 4g + cc (the same k in A and B, which is all the sum needs).
@@ -633,14 +633,39 @@ __device__ __forceinline__ f32x4 mfma_q8(f16x8 a0, f16x8 a1, f16x8 b0, f16x8 b1,
     constexpr int eb = K == 0 ? Q8_EXP_LO : (K == 1 ? Q8_EXP_MID : Q8_EXP_HI);
     return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, b, c, 0, 0, 0, 127 - ea, 0, 127 - eb);
 }
-// the 8 e4m3 bytes of one f16 fragment times 2^e (element j -> byte j)
-__device__ __forceinline__ u32x2 q8_of(f16x8 p, float s) {
-    int lo = 0, hi = 0;
-    lo = __builtin_amdgcn_cvt_pk_fp8_f32((float)p[0] * s, (float)p[1] * s, lo, false);
-    lo = __builtin_amdgcn_cvt_pk_fp8_f32((float)p[2] * s, (float)p[3] * s, lo, true);
-    hi = __builtin_amdgcn_cvt_pk_fp8_f32((float)p[4] * s, (float)p[5] * s, hi, false);
-    hi = __builtin_amdgcn_cvt_pk_fp8_f32((float)p[6] * s, (float)p[7] * s, hi, true);
-    return u32x2{(unsigned)lo, (unsigned)hi};
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef short i16x2 __attribute__((ext_vector_type(2)));
+// The 8 e4m3 bytes of one f16 fragment times 2^E (element j -> byte j), converted from the packed f16 pairs under
+// the scale in one v_cvt_scalef32_pk_fp8_f16 per pair: the instruction divides by its scale operand (2^-E here),
+// rounds to nearest even and keeps e4m3 subnormals and f16 subnormal inputs, so on finite |p 2^E| <= 256 its bytes
+// are those of v_cvt_pk_fp8_f32((float)p * 2^E) (every f16 pattern x the three planes: gp_debug_q8_probe,
+// tests/test_gpu_plane_epilogue.py). VIA_F32: that earlier path (two conversions back, two multiplications and
+// one conversion per pair), kept for the probe's comparison only.
+template <int E, bool VIA_F32 = false>
+__device__ __forceinline__ u32x2 q8_of(f16x8 p) {
+    if constexpr (VIA_F32) {
+        const float s = exp2i(E);
+        int lo = 0, hi = 0;
+        lo = __builtin_amdgcn_cvt_pk_fp8_f32((float)p[0] * s, (float)p[1] * s, lo, false);
+        lo = __builtin_amdgcn_cvt_pk_fp8_f32((float)p[2] * s, (float)p[3] * s, lo, true);
+        hi = __builtin_amdgcn_cvt_pk_fp8_f32((float)p[4] * s, (float)p[5] * s, hi, false);
+        hi = __builtin_amdgcn_cvt_pk_fp8_f32((float)p[6] * s, (float)p[7] * s, hi, true);
+        return u32x2{(unsigned)lo, (unsigned)hi};
+    } else {
+        const float s = exp2i(-E);
+        // each conversion replaces one 16-bit word of its destination and the two of a register replace both: the
+        // destination starts undefined instead of costing a v_mov 0 (an empty asm defines it; its input only keeps
+        // the two asms of a fragment, and those of other fragments, from being merged into one value)
+        i16x2 lo, hi;
+        asm("" : "=v"(lo) : "v"(f16x2{p[0], p[1]}));
+        asm("" : "=v"(hi) : "v"(f16x2{p[4], p[5]}));
+        lo = __builtin_amdgcn_cvt_scalef32_pk_fp8_f16(lo, f16x2{p[0], p[1]}, s, false);
+        lo = __builtin_amdgcn_cvt_scalef32_pk_fp8_f16(lo, f16x2{p[2], p[3]}, s, true);
+        hi = __builtin_amdgcn_cvt_scalef32_pk_fp8_f16(hi, f16x2{p[4], p[5]}, s, false);
+        hi = __builtin_amdgcn_cvt_scalef32_pk_fp8_f16(hi, f16x2{p[6], p[7]}, s, true);
+        return u32x2{__builtin_bit_cast(unsigned, lo), __builtin_bit_cast(unsigned, hi)};
+    }
 }
 // One (chunk, column tile)'s planes as the epilogues hold them between the split and the LDS write
 template <int PL>
@@ -649,27 +674,49 @@ struct ActPlanes {
     u32x2 q[PL == X3Q ? 3 : 1];   // X3Q: the e4m3 bytes of products 0..2's B operands (a_lo8, a_mid8, a_hi8)
 };
 
-// x = h + m + l exactly (x finite, |x| < 65504; f16 subnormals aside)
-__device__ __forceinline__ void split3(float x, _Float16& h, _Float16& m, _Float16& l) {
-#pragma clang fp contract(off)
-    h = (_Float16)x;
-    const float r = x - (float)h;   // exact: x and h agree in sign and leading bits
-    m = (_Float16)r;
-    l = (_Float16)(r - (float)m);   // exact likewise; <= 3 significant bits remain
+// x - (float)h for half HI of the packed pair h, in one v_fma_mix_f32 that reads the f16 operand in place:
+// h * -1 + x, an exact product under the subtraction's single rounding, so the bits (and the sign of a zero) are
+// those of converting h back and subtracting. Written as asm: from C the compiler turns fma(h, -1, x) back into
+// v_cvt_f32_f16 + v_sub_f32.
+template <int HI>
+__device__ __forceinline__ float sub_f16(float x, f16x2 h) {
+    float r;
+    if constexpr (HI)
+        asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r) : "v"(h), "v"(x));
+    else
+        asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(r) : "v"(h), "v"(x));
+    return r;
+}
+// {f16(x[0] - h[0]), f16(x[1] - h[1])}: the same residuals converted to f16 by the instruction that forms them
+// (v_fma_mixlo_f16 / v_fma_mixhi_f16: the residual is exact in fp32, so the conversion is the only rounding)
+__device__ __forceinline__ f16x2 sub_f16_pk(f32x2 x, f16x2 h) {
+    f16x2 d;
+    asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(d) : "v"(h), "v"(x[0]));
+    asm("v_fma_mixhi_f16 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(d) : "v"(h), "v"(x[1]));
+    return d;
 }
 // The three planes of the 32-deep chunk made of two accumulator tiles (u: tile 2c, v: tile 2c+1),
-// times s, in the k order of pack_h16_fragments (as split_pair).
+// times s, in the k order of pack_h16_fragments (as split_pair): x = h + m + l exactly (x finite, |x| < 65504;
+// f16 subnormals aside) with h = f16(x), m = f16(x - h), l = f16(x - h - m). Both residuals are exact (x and h
+// agree in sign and leading bits; <= 3 significant bits remain for l). Two values at a time, each plane's pair
+// packed by the conversion that makes it.
 __device__ __forceinline__ void split3_pair(f32x4 u, f32x4 v, float s, f16x8 (&p)[X3P]) {
 #pragma clang fp contract(off)
     const float x[8] = {u.x * s, u.y * s, u.z * s, u.w * s, v.x * s, v.y * s, v.z * s, v.w * s};
+    f16x2 h[4], m[4], l[4];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        _Float16 h, m, l;
-        split3(x[j], h, m, l);
-        p[0][j] = h;
-        p[1][j] = m;
-        p[2][j] = l;
+    for (int j = 0; j < 4; ++j) {
+        h[j] = __builtin_convertvector(f32x2{x[2 * j], x[2 * j + 1]}, f16x2);
+        const f32x2 r = {sub_f16<0>(x[2 * j], h[j]), sub_f16<1>(x[2 * j + 1], h[j])};
+        m[j] = __builtin_convertvector(r, f16x2);
+        l[j] = sub_f16_pk(r, m[j]);
     }
+    p[0] = __builtin_shufflevector(__builtin_shufflevector(h[0], h[1], 0, 1, 2, 3),
+                                   __builtin_shufflevector(h[2], h[3], 0, 1, 2, 3), 0, 1, 2, 3, 4, 5, 6, 7);
+    p[1] = __builtin_shufflevector(__builtin_shufflevector(m[0], m[1], 0, 1, 2, 3),
+                                   __builtin_shufflevector(m[2], m[3], 0, 1, 2, 3), 0, 1, 2, 3, 4, 5, 6, 7);
+    p[2] = __builtin_shufflevector(__builtin_shufflevector(l[0], l[1], 0, 1, 2, 3),
+                                   __builtin_shufflevector(l[2], l[3], 0, 1, 2, 3), 0, 1, 2, 3, 4, 5, 6, 7);
 }
 // split3_pair into the planes the PL form keeps: X3P the three f16 planes; X3Q hi, mid and the e4m3 planes
 template <int PL>
@@ -679,9 +726,9 @@ __device__ __forceinline__ void split_act(f32x4 u, f32x4 v, float s, ActPlanes<P
     a.h[0] = p[0];
     a.h[1] = p[1];
     if constexpr (PL == X3Q) {
-        a.q[0] = q8_of(p[2], exp2i(Q8_EXP_LO));
-        a.q[1] = q8_of(p[1], exp2i(Q8_EXP_MID));
-        a.q[2] = q8_of(p[0], exp2i(Q8_EXP_HI));
+        a.q[0] = q8_of<Q8_EXP_LO>(p[2]);
+        a.q[1] = q8_of<Q8_EXP_MID>(p[1]);
+        a.q[2] = q8_of<Q8_EXP_HI>(p[0]);
     } else {
         a.h[2] = p[2];
     }
@@ -909,6 +956,13 @@ __device__ __forceinline__ void head_x3_head(const X3Weights& WH, const f16x8* _
     __builtin_amdgcn_sched_barrier(0);
 }
 
+// Entry i of column c's precomputed ColScales in sm.cscl (0 s1, 1 s2, 2 u2, 3 uh, 4 sh), one 4-byte read (ld1: parts
+// of a row read at different places are not merged into a 12-byte read)
+template <int NT, int WV, int PL>
+__device__ __forceinline__ float col_scale(const HeadSmem<NT, WV, PL>& sm, int c, int i) {
+    return ld1(reinterpret_cast<const float*>(&sm.cscl[c][0]) + i);
+}
+
 // PL (taken from sm): X3P the six f16 products; X3Q the hybrid form (w.pe2_q / w.h1p_q must be given)
 template <int NT, int WV, bool PRE = false, bool JVP = false, int PL = X3P>
 __device__ __forceinline__ void head_trunk_x3(const gp_head_weights& w, const float* __restrict__ pobj,
@@ -950,23 +1004,32 @@ __device__ __forceinline__ void head_trunk_x3(const gp_head_weights& w, const fl
     __syncthreads();
     PC_MARK(1);
     // ---- per-candidate exponents: bound1 >= |pose_encoder.0 out|, bound2 >= |pose_encoder.2 out|
+    // LATE_SCALES (the 64-candidate hybrid PC step, which sits at the 256-register limit): the later layers' scales
+    // are read from sm.cscl where they are used (ahead of pose_encoder.2's epilogue and of head layer 1's barrier)
+    // instead of being held from here on: with the shorter epilogues' schedule they were what that kernel spilled.
+    // Every other kernel keeps them in registers (on 16-candidate tiles the late reads cost 0.1 us per launch).
+    constexpr bool LATE_SCALES = PRE && PL == X3Q && NT == 4;
     f32x4 bf[NT];
     float s1[NT], s2[NT], u2[NT], uh[NT], sh[NT];
 #pragma unroll
     for (int ct = 0; ct < NT; ++ct) {
         bf[ct] = ld4(&sm.xin[(ct * 16 + n) * 16 + 4 * q]);
-        ColScales cs;
-        if constexpr (PRE) {
-            const f32x4 a = sm.cscl[ct * 16 + n][0];
-            cs = ColScales{a.x, a.y, a.z, a.w, sm.cscl[ct * 16 + n][1].x};
+        if constexpr (LATE_SCALES) {
+            s1[ct] = col_scale(sm, ct * 16 + n, 0);
         } else {
-            cs = split_col_scales(xin_row_absmax(bf[ct]), hs);
+            ColScales cs;
+            if constexpr (PRE) {
+                const f32x4 a = sm.cscl[ct * 16 + n][0];
+                cs = ColScales{a.x, a.y, a.z, a.w, sm.cscl[ct * 16 + n][1].x};
+            } else {
+                cs = split_col_scales(xin_row_absmax(bf[ct]), hs);
+            }
+            s1[ct] = cs.s1;
+            s2[ct] = cs.s2;
+            u2[ct] = cs.u2;
+            uh[ct] = cs.uh;
+            sh[ct] = cs.sh;
         }
-        s1[ct] = cs.s1;
-        s2[ct] = cs.s2;
-        u2[ct] = cs.u2;
-        uh[ct] = cs.uh;
-        sh[ct] = cs.sh;
     }
     // ---- pose_encoder.0 (9 -> 256) in fp32, one k-group; ReLU, scale, split into the chunk planes
 #pragma unroll
@@ -1017,6 +1080,13 @@ __device__ __forceinline__ void head_trunk_x3(const gp_head_weights& w, const fl
     // the epilogue's planes are made before the alias barrier (a wave that finished its stream early does
     // this VALU work while it waits for the last one) and only written after it (profiles/r4/ab_epi_early.json)
     ActPlanes<PL> pls[CPW][NT];
+    if constexpr (LATE_SCALES) {
+#pragma unroll
+        for (int ct = 0; ct < NT; ++ct) {
+            s2[ct] = col_scale(sm, ct * 16 + n, 1);
+            u2[ct] = col_scale(sm, ct * 16 + n, 2);
+        }
+    }
 #pragma unroll
     for (int c = 0; c < CPW; ++c) {
         const int Ta = T2[2 * c];
@@ -1043,6 +1113,13 @@ __device__ __forceinline__ void head_trunk_x3(const gp_head_weights& w, const fl
 #pragma unroll
         for (int ct = 0; ct < NT; ++ct)
             store_act<PL, NT>(act2h, T2[2 * c] >> 1, ct, lane, pls[c][ct]);
+    if constexpr (LATE_SCALES) {   // in front of the barrier, whose wait covers the reads
+#pragma unroll
+        for (int ct = 0; ct < NT; ++ct) {
+            uh[ct] = col_scale(sm, ct * 16 + n, 3);
+            sh[ct] = col_scale(sm, ct * 16 + n, 4);
+        }
+    }
     __syncthreads();
     PC_MARK(4);
     // ---- head layer 1 (pose block 256 -> 3x256) head by head, each followed by its layer-2 partials

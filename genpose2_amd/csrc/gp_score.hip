@@ -854,3 +854,30 @@ extern "C" int gp_scale_forward(const gp_scale_weights* w, const float* axes, co
     hipLaunchKernelGGL(scale_kernel, dim3(b), dim3(HT), 0, stream, *w, axes, pts_feat, length);
     return gp_check_launch("scale_kernel");
 }
+
+// ============================================================================ e4m3 plane conversion probe
+// q8_of on caller-given f16 bit patterns: a thread converts one fragment of eight (patterns past n read as zero,
+// their bytes are not written).
+template <bool VIA_F32>
+__global__ __launch_bounds__(HT) void q8_probe_kernel(const uint16_t* __restrict__ bits, int n, int plane,
+                                                      uint8_t* __restrict__ out) {
+    const long long i0 = ((long long)blockIdx.x * HT + threadIdx.x) * 8;
+    f16x8 p;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) p[j] = __builtin_bit_cast(_Float16, i0 + j < n ? bits[i0 + j] : (uint16_t)0);
+    const u32x2 b = plane == 0 ? q8_of<Q8_EXP_HI, VIA_F32>(p)
+                               : (plane == 1 ? q8_of<Q8_EXP_MID, VIA_F32>(p) : q8_of<Q8_EXP_LO, VIA_F32>(p));
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+        if (i0 + j < n) out[i0 + j] = (uint8_t)(b[j >> 2] >> (8 * (j & 3)));
+}
+
+extern "C" int gp_debug_q8_probe(const uint16_t* f16_bits, int n, int plane, uint8_t* q8, uint8_t* q8_via_f32,
+                                 hipStream_t stream) {
+    GP_REQUIRE(f16_bits && q8 && q8_via_f32 && n >= 0 && plane >= 0 && plane < 3, "debug_q8_probe: bad arguments");
+    if (!n) return GP_OK;
+    const int nwg = (int)(((long long)n + 8 * HT - 1) / (8 * HT));
+    hipLaunchKernelGGL(q8_probe_kernel<false>, dim3(nwg), dim3(HT), 0, stream, f16_bits, n, plane, q8);
+    hipLaunchKernelGGL(q8_probe_kernel<true>, dim3(nwg), dim3(HT), 0, stream, f16_bits, n, plane, q8_via_f32);
+    return gp_check_launch("q8_probe_kernel");
+}

@@ -273,6 +273,12 @@ int gp_energy_score_eval(const gp_head_weights *w, const gp_head_grad_weights *g
                          const float *tproj_row, float sigma, const float *x, int rows, int k,
                          float *score, float *energy, hipStream_t stream);
 
+/* Probe of the hybrid trunk's e4m3 activation-plane conversion (plane 0 hi: x 2^-7, 1 mid: x 2^4, 2 lo: x 2^16):
+ * for n f16 bit patterns (device), q8 = the bytes the trunk's helper makes (packed f16 converted under the scale),
+ * q8_via_f32 = the bytes of v_cvt_pk_fp8_f32((float)v * 2^e); n bytes each (device). Only compares conversions. */
+int gp_debug_q8_probe(const uint16_t *f16_bits, int n, int plane, uint8_t *q8, uint8_t *q8_via_f32,
+                      hipStream_t stream);
+
 /* ===================================================================== PC sampler
  * cond_pc_sampler (samplers.py:113-177) for R = b*k rows over T steps, fused per step:
  * [finish step i-1: Langevin corrector with the batch-mean score norm, renormalise,
