@@ -169,6 +169,13 @@ _SIGS: Dict[str, tuple] = {
     "gp_bbox_length": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "gp_rank_aggregate": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_int, c_void_p, c_void_p,
                                   c_void_p, c_void_p]),
+    "gp_frame_mask_stats": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "gp_frame_crop_boxes": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "gp_frame_objects_workspace_size": (c_size_t, [c_int, c_int]),
+    "gp_frame_objects": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_float,
+                                 c_float, c_float, c_float, c_float, c_uint64, c_void_p, c_void_p, c_void_p,
+                                 c_void_p, c_void_p, c_size_t, c_void_p]),
+    "gp_frame_roi_rgb": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p]),
 }
 
 EXPORTED = tuple(_SIGS)

@@ -1,0 +1,90 @@
+"""Frame in, poses and sizes out: the counterpart of runners/infer.py ``GenPose2``.
+
+``GenPose2.inference(data, prev_pose, tracking, tracking_T0)`` runs the front end (frontend.frame_objects) once
+and the ``EvaluationPipeline`` stages on its batch: score sampling (warm-started from ``prev_pose``), energy
+ranking with get_energy(T=None), aggregation, size. The reference calls ``get_objects()`` once per stage, so its
+EnergyNet and size stage see a fresh random sample of the points; here every stage reads the same sample.
+"""
+from __future__ import annotations
+
+from typing import Dict, Optional, Tuple, Union
+
+import torch
+
+from . import device as dev
+from .config import GenPoseConfig
+from .frontend import InferDataset
+from .runner import EvaluationPipeline
+
+
+def default_config(**kw) -> GenPoseConfig:
+    """runners/infer.py:78-90: the ODE sampler from T0 = 0.55, 50 candidates, seed 0. ``dino`` is 'none' (the
+    reference's 'pointwise' needs the DINOv3 backbone, which is not part of this build)."""
+    base = dict(sampler_mode=["ode"], T0=0.55, seed=0, eval_repeat_num=50, dino="none")
+    base.update(kw)
+    return GenPoseConfig(**base)
+
+
+def pose_representation(pose: torch.Tensor) -> torch.Tensor:
+    """(B,4,4) [R t; 0 1] -> (B,9) [R[:, :, 0] | R[:, :, 1] | t] (utils/misc.py get_pose_representation for
+    rot_matrix, then the translation)."""
+    return torch.cat([pose[:, :3, 0], pose[:, :3, 1], pose[:, :3, 3]], dim=-1)
+
+
+class GenPose2:
+    """``score_model_path`` / ``energy_model_path`` / ``scale_model_path``: reference checkpoints. A ``None``
+    score or energy path keeps that agent's synthetic weights (as ``PoseNet`` does); without a scale path there
+    is no ScaleNet and the size is the points' bounding box in the estimated frame."""
+
+    def __init__(self, score_model_path: Optional[str], energy_model_path: Optional[str] = None,
+                 scale_model_path: Optional[str] = None, cfg: Optional[GenPoseConfig] = None):
+        cfg = default_config() if cfg is None else cfg
+        self.cfg = cfg.copy(pretrained_score_model_path=score_model_path,
+                            pretrained_energy_model_path=energy_model_path,
+                            pretrained_scale_model_path=scale_model_path)
+        self.cfg.validate()
+        self.pipeline = EvaluationPipeline(self.cfg, with_energy=True, with_scale=scale_model_path is not None)
+        for agent, path in ((self.score_agent, score_model_path), (self.energy_agent, energy_model_path),
+                            (self.scale_agent, scale_model_path)):
+            if agent is not None and path is not None:
+                agent.load_ckpt(model_dir=path, model_path=True, load_model_only=True)
+
+    score_agent = property(lambda self: self.pipeline.score_agent)
+    energy_agent = property(lambda self: self.pipeline.energy_agent)
+    scale_agent = property(lambda self: self.pipeline.scale_agent)
+
+    @torch.no_grad()
+    def inference(self, data: Union[InferDataset, Dict[str, torch.Tensor]], prev_pose=None, tracking: bool = False,
+                  tracking_T0: float = 0.15) -> Tuple[torch.Tensor, torch.Tensor]:
+        """-> (final_pose (B,4,4), final_length (B,3)), objects in ascending mask id (runners/infer.py:276-310).
+
+        ``data``: an ``InferDataset`` (its ``get_objects()`` runs once) or a batch ``frame_objects`` returned.
+        ``prev_pose`` (B,4,4) (or the reference's one-element list of it) warm-starts the sampler at
+        [R[:, 0] | R[:, 1] | t - pts_center]; the start time is ``tracking_T0`` only when ``tracking`` is set as
+        well, else cfg.T0 -- as the reference does."""
+        batch = data.get_objects() if hasattr(data, "get_objects") else data
+        pts = batch["pts"]
+        B = int(pts.shape[0])
+        if B == 0:
+            return pts.new_zeros((0, 4, 4)), pts.new_zeros((0, 3))
+        init_x = None
+        if prev_pose is not None:
+            if isinstance(prev_pose, (list, tuple)):
+                if len(prev_pose) != 1:
+                    raise ValueError("prev_pose as a list holds one (B,4,4) tensor: one frame per call")
+                prev_pose = prev_pose[0]
+            prev_pose = torch.as_tensor(prev_pose).to(pts.device, torch.float32)
+            if tuple(prev_pose.shape) != (B, 4, 4):
+                raise ValueError(f"prev_pose must be ({B},4,4), got {tuple(prev_pose.shape)}")
+            init_x = pose_representation(prev_pose)
+            init_x[:, -3:] -= batch["pts_center"]
+        T0 = tracking_T0 if tracking and prev_pose is not None else None
+        out = self.pipeline.run(batch, init_x=init_x, T0=T0, energy_T=None)
+        final_pose = out.aggregated
+        length = out.length if out.length is not None else dev.bbox_length(pts, final_pose)
+        return final_pose, length
+
+
+def create_genpose2(score_model_path: Optional[str], energy_model_path: Optional[str] = None,
+                    scale_model_path: Optional[str] = None, cfg: Optional[GenPoseConfig] = None) -> GenPose2:
+    return GenPose2(score_model_path, energy_model_path, scale_model_path, cfg)

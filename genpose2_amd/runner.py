@@ -48,10 +48,13 @@ class EvaluationPipeline:
         self.scale_agent = PoseNet(cfg.copy(agent_type="scale")).eval() if with_scale else None
         self._side = None
 
-    def run(self, batch: Dict[str, torch.Tensor]) -> StageOutputs:
+    def run(self, batch: Dict[str, torch.Tensor], init_x: Optional[torch.Tensor] = None, T0: Optional[float] = None,
+            energy_T: Optional[float] = 1e-5) -> StageOutputs:
         """One batch through the stages. The energy network's point encoder depends only on the
         points, so it runs on a side stream concurrently with the score sampler (started after the
-        score encoder, whose kernels want the whole chip) and is joined before the energy evaluation."""
+        score encoder, whose kernels want the whole chip) and is joined before the energy evaluation.
+        ``init_x`` (B,9) and ``T0`` are pred_func's warm start and start time (default: the prior at
+        cfg.T0); ``energy_T`` is get_energy's T (None draws the per-object times, as runners/infer.py does)."""
         cfg = self.cfg
         data = dict(batch)
         edata = None
@@ -74,7 +77,8 @@ class EvaluationPipeline:
                     self.energy_agent.encode_func(edata)
             self.score_agent.after_encode = start_energy_encoder
         try:
-            pred_pose, _ = self.score_agent.pred_func(data=data, repeat_num=cfg.eval_repeat_num, T0=cfg.T0,
+            pred_pose, _ = self.score_agent.pred_func(data=data, repeat_num=cfg.eval_repeat_num,
+                                                      T0=cfg.T0 if T0 is None else T0, init_x=init_x,
                                                       return_average_res=False, return_process=False)
         finally:
             self.score_agent.after_encode = None
@@ -84,7 +88,7 @@ class EvaluationPipeline:
             edata["pts_feat"].record_stream(main)
             if "_energy_pobj" in edata:
                 edata["_energy_pobj"][1].record_stream(main)
-            out.energy = self.energy_agent.get_energy(data=edata, pose_samples=pred_pose, T=1e-5, mode="test",
+            out.energy = self.energy_agent.get_energy(data=edata, pose_samples=pred_pose, T=energy_T, mode="test",
                                                       extract_feature=False)
         energy = out.energy if out.energy is not None else torch.ones(*pred_pose.shape[:2], 2,
                                                                       device=pred_pose.device)

@@ -562,6 +562,41 @@ int gp_points_mean(const float *pts, int b, int n, int c, float *out, hipStream_
 int gp_bbox_length(const float *pcl, int b, int n, int c, const float *pose, float *length,
                    hipStream_t stream);
 
+/* ===================================================================== RGB-D front end
+ * One camera frame -> the per-object batch (datasets/datasets_infer.py InferDataset.get_objects; the rules
+ * are in DESIGN.md "RGB-D front end"). depth (h,w) float32 metres, color (h,w,3) uint8, mask (h,w) uint8 with
+ * 255 = background and every other value an object id; all on the device, none modified. Call sequence:
+ * gp_frame_mask_stats, copy the 256 x 5 statistics to the host, gp_frame_crop_boxes (host), upload ids and
+ * boxes, gp_frame_objects and gp_frame_roi_rgb, gp_points_mean; read `count` to reject objects with fewer
+ * than 10 valid points.
+ *
+ * Per mask value v: stats[v] = {count, rmin, rmax, cmin, cmax} (int32 (256,5)); an absent value has
+ * {0, h, -1, w, -1}. Integer atomics only: the result does not depend on their order. */
+int gp_frame_mask_stats(const uint8_t *mask, int h, int w, int *stats, hipStream_t stream);
+/* HOST function (no device work; h, w > 40): the object ids present (ascending, 255 left out) -> ids_out
+ * (up to 255) and boxes_out (up to 255 x 3: centre x, centre y, scale of the square crop window, all exact
+ * in float32) from a host copy of the statistics; *n_out = their number. The window is get_bbox's
+ * (utils/sgpa_utils.py: multiples of 40 pixels, at most min(h,w) - 40, shifted back inside the image), centre
+ * and scale are aug_bbox_eval's (utils/datasets_utils.py). */
+int gp_frame_crop_boxes(const int *stats_host, int h, int w, int *ids_out, float *boxes_out, int *n_out);
+/* Bytes of gp_frame_objects' workspace for b objects and an img_size x img_size crop. */
+size_t gp_frame_objects_workspace_size(int b, int img_size);
+/* Per object (ids, boxes (b,3) on the device): the crop pixels whose nearest source pixel carries the id and a
+ * depth in (0, max_depth], in row-major crop order (list V, count[b] = its length c), n_pts of them sampled
+ * (c < n_pts: element j is V[j mod c]; else the n_pts smallest of (Philox4x32-10 word 0 of counter
+ * {e, id, 0, 0x53414D50} under key = seed's halves, e) in that order) and back-projected with the given
+ * (already scaled) intrinsics, each float32 operation rounded on its own -> pts (b,n_pts,3), roi_xs (crop row)
+ * and roi_ys (crop column) (b,n_pts) int32, count (b) int32. n_pts <= 2048, img_size even and >= 14. An object
+ * with c = 0 gets zeros. */
+int gp_frame_objects(const float *depth, const uint8_t *mask, int h, int w, const int *ids, const float *boxes,
+                     int b, int img_size, int n_pts, float fx, float fy, float cx, float cy, float max_depth,
+                     uint64_t seed, float *pts, int *roi_xs, int *roi_ys, int *count, void *workspace,
+                     size_t workspace_bytes, hipStream_t stream);
+/* roi_rgb (b,3,img_size,img_size) float32: the bilinear crop of color (taps outside the image are 0), rounded
+ * to a uint8 level as floor(value + 0.5), then (level / 255 - mean) / std with the ImageNet constants. */
+int gp_frame_roi_rgb(const uint8_t *color, int h, int w, const float *boxes, int b, int img_size, float *roi_rgb,
+                     hipStream_t stream);
+
 /* ===================================================================== weight packing
  * The load path of PoseNet.load_ckpt -> load_state_dict (posenet_agent.py:171-203) for the --dino none
  * models, without Python: a model's state-dict tensors (HOST float32 arrays named by the reference's
