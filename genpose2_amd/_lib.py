@@ -37,6 +37,16 @@ class ScaleWeights(ctypes.Structure):
                                        "ft2_b")]
 
 
+class DinoBlock(ctypes.Structure):
+    _fields_ = [(n, c_void_p) for n in ("ln1_w", "ln1_b", "qkv_w", "qkv_b", "proj_w", "proj_b", "ln2_w", "ln2_b",
+                                       "w12_w", "w12_b", "w3_w", "w3_b", "qkv_h", "proj_h", "w12_h", "w3_h")]
+
+
+class DinoWeights(ctypes.Structure):
+    _fields_ = [(n, c_void_p) for n in ("patch_w", "patch_b", "cls_token", "storage_tokens", "norm_w", "norm_b",
+                                       "rope")] + [("rope_hp", c_int), ("rope_wp", c_int), ("blocks", DinoBlock * 12)]
+
+
 # name -> (restype, argtypes)
 _SIGS: Dict[str, tuple] = {
     "gp_last_error": (ctypes.c_char_p, []),
@@ -163,6 +173,11 @@ _SIGS: Dict[str, tuple] = {
     "gp_img_geo_table": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p]),
     "gp_gather_patch_points": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int,
                                        c_void_p, c_void_p]),
+    "gp_dino_workspace_size": (c_size_t, [c_int, c_int, c_int]),
+    "gp_dino_rope_table": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "gp_dino_forward": (c_int, [ctypes.POINTER(DinoWeights), c_void_p, c_int, c_int, c_int, c_int,
+                                ctypes.POINTER(c_int), ctypes.POINTER(c_void_p), c_int, c_void_p, c_size_t,
+                                c_void_p]),
     "gp_scale_forward": (c_int, [ctypes.POINTER(ScaleWeights), c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "gp_randn": (c_int, [c_uint64, ctypes.c_uint32, c_int, c_int, c_void_p, c_void_p]),
     "gp_points_mean": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),

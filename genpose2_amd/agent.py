@@ -59,9 +59,10 @@ class PoseNet:
         self._gen = torch.Generator(device=self.device)
         self._gen.manual_seed(self.cfg.noise_seed)
         self.weights_source = f"synthetic(seed={self.cfg.seed})"
-        # --dino pointwise: the frozen DINOv3 backbone (posenet.py:56-62) is not part of this build; a caller
-        # that has it sets it here (an object with the reference's get_intermediate_layers), or passes its
-        # output as data["dino_layers"]
+        # --dino pointwise: the frozen DINOv3 backbone (posenet.py:56-62), a dino.DinoBackbone built by load_ckpt
+        # from the checkpoint's "dino." keys or by load_dino from the stand-alone pretrain file. The synthetic
+        # weights have none: data["dino_layers"] then carries the backbone's output (any object with the
+        # reference's get_intermediate_layers may also be set here)
         self.dino = None
         self._build(weights.synthetic_state_dict(self.weights_kind, seed=self.cfg.seed))
 
@@ -77,9 +78,11 @@ class PoseNet:
     # ------------------------------------------------------------------ model construction
     def _build(self, sd: weights.StateDict) -> None:
         if self.pointwise:
-            # a --dino pointwise checkpoint also holds the frozen DINOv3 backbone (posenet.py:56-62): its
-            # intermediate layers are this path's input (data["dino_layers"], or self.dino)
-            sd = {k: v for k, v in sd.items() if not k.startswith("dino.")}
+            # a --dino pointwise checkpoint also holds the frozen DINOv3 backbone (posenet.py:56-62) as "dino."
+            # keys: it runs on device (dino.DinoBackbone) ahead of the ImgEncoder
+            sd, dino_sd = weights.split_dino(sd)
+            if dino_sd:
+                self.load_dino(dino_sd)
         weights.check_keys(sd, self.weights_kind)
         self.state_dict = sd
         self._pc_cache = {}                        # T -> (step table, tproj); energy t -> time row
@@ -96,6 +99,20 @@ class PoseNet:
         else:
             self.encoder = self.heads = None
             self.scale = dev.ScaleModel(sd, self.device)
+
+    def load_dino(self, path_or_state_dict) -> None:
+        """The DINOv3 ViT-S+/16 backbone into ``self.dino`` from the stand-alone pretrain file (a path; keys
+        without a prefix) or from a state dict in that format (a "dino." prefix is accepted too)."""
+        if not self.pointwise:
+            raise ValueError("the DINOv3 backbone belongs to cfg.dino == 'pointwise' score / energy agents")
+        from .dino import DinoBackbone
+        sd = path_or_state_dict
+        if isinstance(sd, (str, os.PathLike)):
+            sd = weights.load_checkpoint(os.fspath(sd))
+        sd = {k: (v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)) for k, v in sd.items()}
+        if any(k.startswith(weights.DINO_PREFIX) for k in sd):
+            sd = weights.split_dino(sd)[1]
+        self.dino = DinoBackbone(sd, self.device)
 
     def load_ckpt(self, name=None, model_dir=None, model_path=False, load_model_only=False):
         """posenet_agent.py:171-203 path resolution; loads with torch.load(weights_only=True)."""

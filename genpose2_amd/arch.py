@@ -89,6 +89,15 @@ IMG_LAYERS = (2, 6, 11)               # get_intermediate_layers(n=[2, 6, 11], no
 IMG_PATCH_PX = 14                     # roi_xs // 14, roi_ys // 14
 IMG_REL_EMB = (2 * (IMG_GRID - 1)) ** 2   # nn.Embedding(max_rel * max_rel, dim // 4): 900 rows
 
+# The frozen DINOv3 backbone ahead of the ImgEncoder (posenet.py:56-62): dinov3_vits16plus
+DINO_BLOCKS = 12
+DINO_HEADS = 6
+DINO_HEAD_DIM = 64
+DINO_PATCH = 16
+DINO_STORAGE = 4                      # storage (register) tokens after the cls token
+DINO_HIDDEN = 1536                    # SwiGLU hidden width
+DINO_MAX_PATCHES = 1024               # gp_dino_forward's limit on (H/16)(W/16)
+
 
 def fus_sa_branches() -> List[List[SABranch]]:
     """sa_branches() with the 384 image-feature channels entering level 0 (pointnet2.py:281-285:

@@ -493,13 +493,27 @@ __global__ __launch_bounds__(SL_THREADS) void linear_split_kernel(SplitLinArgs a
         const int pc = (JT * wt + j) * 16 + nn, r = m0 + pc;
         const float u = exp2i(eT[pc] - 14 - ew);
         float ym = 0.f;
+        if constexpr (ACT == 5) {   // SwiGLU: tiles (i, i + 1) = (gate, up) of hidden tile (T0 + 4 wo + i) / 2
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
+            for (int i = 0; i < 4; i += 2) {
+                const int T = T0 + 4 * wo + i, o = T * 16 + 4 * q;
+                if (o >= a.n || r >= a.m) continue;
+                const f32x4 g = acc[i][j] * u + ld4(a.bias + o), up = acc[i + 1][j] * u + ld4(a.bias + o + 16);
+                f32x4 v;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[e] = g[e] / (1.0f + expf(-g[e])) * up[e];
+                ym = fmaxf(ym, fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))));
+                st4(a.y + (size_t)r * a.ldy + (T >> 1) * 16 + 4 * q, v);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < (ACT == 5 ? 0 : 4); ++i) {
             const int o = (T0 + 4 * wo + i) * 16 + 4 * q;
             if (o >= a.n || r >= a.m) continue;
             f32x4 v = acc[i][j] * u + ld4(a.bias + o);
+            if (ACT == 4) v += ld4(a.y + (size_t)r * a.ldy + o);   // y += : each element is read and written by this lane only
             if (ACT == 1) v = relu4(v);
-            if (ACT >= 2) v = f32x4{sigmoidf(v.x), sigmoidf(v.y), sigmoidf(v.z), sigmoidf(v.w)};
+            if (ACT == 2 || ACT == 3) v = f32x4{sigmoidf(v.x), sigmoidf(v.y), sigmoidf(v.z), sigmoidf(v.w)};
             if (ACT == 3) {   // GatedAttentionFusion's mix: g * cur + (1 - g) * att, x = [cur | att]
 #pragma clang fp contract(off)
                 const f32x4 cu = ld4(a.x + (size_t)r * a.ldx + o), at = ld4(a.x + (size_t)r * a.ldx + a.n + o);
@@ -536,10 +550,12 @@ extern "C" int gp_linear_split(const float* x, int ldx, int m, int k, const int3
                                int act, float* y, int ldy, float* rmax, int flags, float* ymax, hipStream_t st) {
     GP_REQUIRE(x && wpk && bias && y && rmax && m >= 0, "linear_split: null pointer");
     GP_REQUIRE(k >= 32 && k % 32 == 0 && n >= 16 && n % 16 == 0, "linear_split: k=%d (multiple of 32), n=%d (of 16)", k, n);
-    GP_REQUIRE(ldx >= k && ldy >= n && ldx % 4 == 0 && ldy % 4 == 0, "linear_split: strides ldx=%d ldy=%d", ldx, ldy);
+    GP_REQUIRE(act >= 0 && act <= 5 && (flags & ~GP_LINEAR_RMAX_GIVEN) == 0, "linear_split: act %d flags %d", act, flags);
+    GP_REQUIRE(act != 5 || n % 32 == 0, "linear_split: SwiGLU (act 5) pairs 16-output tiles, n=%d must be a multiple of 32", n);
+    GP_REQUIRE(ldx >= k && ldy >= (act == 5 ? n / 2 : n) && ldx % 4 == 0 && ldy % 4 == 0,
+               "linear_split: strides ldx=%d ldy=%d", ldx, ldy);
     GP_REQUIRE(((uintptr_t)x | (uintptr_t)wpk | (uintptr_t)y | (uintptr_t)bias) % 16 == 0,
                "linear_split: pointers must be 16-byte aligned");
-    GP_REQUIRE(act >= 0 && act <= 3 && (flags & ~GP_LINEAR_RMAX_GIVEN) == 0, "linear_split: act %d flags %d", act, flags);
     GP_REQUIRE(act != 3 || k == 2 * n, "linear_split: the gate mix (act 3) takes x = [cur | att], k = 2n (k=%d n=%d)", k, n);
     if (!m) return GP_OK;
     if (!(flags & GP_LINEAR_RMAX_GIVEN)) {
@@ -558,7 +574,9 @@ extern "C" int gp_linear_split(const float* x, int ldx, int m, int k, const int3
         if (act == 0) hipLaunchKernelGGL((linear_split_kernel<WO, 0, JT>), grid, dim3(SL_THREADS), lds, st, a); \
         else if (act == 1) hipLaunchKernelGGL((linear_split_kernel<WO, 1, JT>), grid, dim3(SL_THREADS), lds, st, a); \
         else if (act == 2) hipLaunchKernelGGL((linear_split_kernel<WO, 2, JT>), grid, dim3(SL_THREADS), lds, st, a); \
-        else hipLaunchKernelGGL((linear_split_kernel<WO, 3, JT>), grid, dim3(SL_THREADS), lds, st, a); \
+        else if (act == 3) hipLaunchKernelGGL((linear_split_kernel<WO, 3, JT>), grid, dim3(SL_THREADS), lds, st, a); \
+        else if (act == 4) hipLaunchKernelGGL((linear_split_kernel<WO, 4, JT>), grid, dim3(SL_THREADS), lds, st, a); \
+        else hipLaunchKernelGGL((linear_split_kernel<WO, 5, JT>), grid, dim3(SL_THREADS), lds, st, a); \
     }
     if (npad % 256 == 0 && sl_wide_tokens(m, npad)) GP_LSPLIT(4, 8)
     else if (npad % 256 == 0) GP_LSPLIT(4, 4)

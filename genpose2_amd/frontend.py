@@ -80,6 +80,15 @@ def scaled_intrinsics(intr: Dict[str, float], h: int, w: int):
             float(np.float32(intr["cx"]) * sx), float(np.float32(intr["cy"]) * sy))
 
 
+def check_img_size(img_size) -> int:
+    """The crop size rule: a positive multiple of 14 (the reference's 224: 16 x 16 windows of 14 pixels for the
+    patch -> point gather) or of 16 (256: what the DINOv3 backbone of --dino pointwise needs, 16 x 16 patches)."""
+    S = int(img_size)
+    if S < 14 or (S % 14 != 0 and S % 16 != 0):
+        raise ValueError(f"img_size must be a positive multiple of 14 or of 16, got {img_size}")
+    return S
+
+
 @torch.no_grad()
 def frame_objects(depth, color, mask, intrinsics, img_size: int = 224, n_pts: int = 1024, max_depth: float = 4.0,
                   seed: int = 0, device: Union[str, torch.device] = "cuda") -> Dict[str, torch.Tensor]:
@@ -95,9 +104,7 @@ def frame_objects(depth, color, mask, intrinsics, img_size: int = 224, n_pts: in
         raise ValueError(f"the front end runs on a HIP device (got {device}); there is no CPU fallback")
     if device.index is None:
         device = torch.device("cuda", torch.cuda.current_device())
-    S, n_pts = int(img_size), int(n_pts)
-    if S < 14 or S % 14 != 0:
-        raise ValueError(f"img_size must be a positive multiple of 14, got {img_size}")
+    S, n_pts = check_img_size(img_size), int(n_pts)
     if not 1 <= n_pts <= MAX_PTS:
         raise ValueError(f"n_pts must be in 1..{MAX_PTS}, got {n_pts}")
     mask = _image(mask, "mask", torch.uint8, (), device)

@@ -11,15 +11,17 @@ from typing import Dict, Optional, Tuple, Union
 
 import torch
 
-from . import device as dev
+from . import arch, device as dev
 from .config import GenPoseConfig
 from .frontend import InferDataset
 from .runner import EvaluationPipeline
 
 
 def default_config(**kw) -> GenPoseConfig:
-    """runners/infer.py:78-90: the ODE sampler from T0 = 0.55, 50 candidates, seed 0. ``dino`` is 'none' (the
-    reference's 'pointwise' needs the DINOv3 backbone, which is not part of this build)."""
+    """runners/infer.py:78-90: the ODE sampler from T0 = 0.55, 50 candidates, seed 0. ``dino`` stays 'none' by
+    default; the reference's shipped configuration is ``default_config(dino="pointwise")`` with checkpoints that
+    carry the DINOv3 backbone ("dino." keys, or ``PoseNet.load_dino``) and ``InferDataset(..., img_size=256)``:
+    the backbone then runs on device on the frame's ``roi_rgb`` (genpose2_amd/dino.py)."""
     base = dict(sampler_mode=["ode"], T0=0.55, seed=0, eval_repeat_num=50, dino="none")
     base.update(kw)
     return GenPoseConfig(**base)
@@ -53,6 +55,17 @@ class GenPose2:
     energy_agent = property(lambda self: self.pipeline.energy_agent)
     scale_agent = property(lambda self: self.pipeline.scale_agent)
 
+    @staticmethod
+    def check_pointwise_size(h: int, w: int) -> None:
+        """--dino pointwise: the ImgEncoder is built for 256 patches, so the backbone's input must be 16 x 16
+        patches of 16 pixels."""
+        h, w = int(h), int(w)
+        if h % arch.DINO_PATCH or w % arch.DINO_PATCH or \
+                (h // arch.DINO_PATCH) * (w // arch.DINO_PATCH) != arch.IMG_PATCHES:
+            raise ValueError(f"dino='pointwise' needs roi_rgb of {arch.IMG_PATCHES} patches of {arch.DINO_PATCH} pixels "
+                             f"(256 x 256), got {h} x {w}: build the frame with InferDataset(..., img_size=256) "
+                             f"(or frame_objects(..., img_size=256))")
+
     @torch.no_grad()
     def inference(self, data: Union[InferDataset, Dict[str, torch.Tensor]], prev_pose=None, tracking: bool = False,
                   tracking_T0: float = 0.15) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -62,7 +75,12 @@ class GenPose2:
         ``prev_pose`` (B,4,4) (or the reference's one-element list of it) warm-starts the sampler at
         [R[:, 0] | R[:, 1] | t - pts_center]; the start time is ``tracking_T0`` only when ``tracking`` is set as
         well, else cfg.T0 -- as the reference does."""
+        if self.cfg.dino == "pointwise" and hasattr(data, "get_objects") and hasattr(data, "_img_size"):
+            self.check_pointwise_size(data._img_size, data._img_size)   # before the front end launches anything
         batch = data.get_objects() if hasattr(data, "get_objects") else data
+        if self.cfg.dino == "pointwise" and batch.get("dino_layers") is None \
+                and batch.get("point_rgb_feat") is None and batch.get("roi_rgb") is not None:
+            self.check_pointwise_size(*batch["roi_rgb"].shape[-2:])
         pts = batch["pts"]
         B = int(pts.shape[0])
         if B == 0:

@@ -47,6 +47,27 @@ class EvaluationPipeline:
         self.energy_agent = PoseNet(cfg.copy(agent_type="energy")).eval() if with_energy else None
         self.scale_agent = PoseNet(cfg.copy(agent_type="scale")).eval() if with_scale else None
         self._side = None
+        self._dino_same = None   # ((id(score backbone), id(energy backbone)), their weights are byte-identical)
+
+    def shared_dino_layers(self, batch: Dict[str, torch.Tensor]):
+        """--dino pointwise with a backbone in both agents: when the two backbones' weights are byte-identical
+        (compared once per pair of backbones) and the batch brings neither ``dino_layers`` nor
+        ``point_rgb_feat``, the backbone's layers of ``roi_rgb`` computed ONCE, for both agents (the reference
+        runs its frozen backbone once per agent); else None and each agent runs its own."""
+        s, e = self.score_agent, self.energy_agent
+        if e is None or not s.pointwise or s.dino is None or e.dino is None:
+            return None
+        if batch.get("dino_layers") is not None or batch.get("point_rgb_feat") is not None \
+                or batch.get("roi_rgb") is None:
+            return None
+        key = (id(s.dino), id(e.dino))
+        if self._dino_same is None or self._dino_same[0] != key:
+            same = s.dino is e.dino or (hasattr(s.dino, "same_weights") and type(s.dino) is type(e.dino)
+                                        and s.dino.same_weights(e.dino))
+            self._dino_same = (key, bool(same))
+        if not self._dino_same[1] or getattr(s.dino, "arith", None) != getattr(e.dino, "arith", None):
+            return None
+        return s.dino_layers({"roi_rgb": batch["roi_rgb"]})
 
     def run(self, batch: Dict[str, torch.Tensor], init_x: Optional[torch.Tensor] = None, T0: Optional[float] = None,
             energy_T: Optional[float] = 1e-5) -> StageOutputs:
@@ -58,6 +79,10 @@ class EvaluationPipeline:
         cfg = self.cfg
         data = dict(batch)
         edata = None
+        layers = self.shared_dino_layers(batch)
+        if layers is not None:
+            batch = dict(batch, dino_layers=layers)
+            data["dino_layers"] = layers
         if self.energy_agent is not None:
             main = torch.cuda.current_stream(batch["pts"].device)
             if self._side is None:

@@ -19,7 +19,7 @@ import numpy as np
 from . import arch
 
 StateDict = Dict[str, np.ndarray]
-_KIND_ID = {"score": 1, "energy": 2, "scale": 3, "score_pointwise": 4, "energy_pointwise": 5}
+_KIND_ID = {"score": 1, "energy": 2, "scale": 3, "score_pointwise": 4, "energy_pointwise": 5, "dino": 6}
 
 
 # ---------------------------------------------------------------- manifest
@@ -98,12 +98,92 @@ def img_encoder_manifest() -> List[Tuple[str, Tuple[int, ...], str]]:
             (f"{p}.geo_weight", (), "const:0.2"), (f"{p}.edge_weight", (), "const:0.1")]
 
 
+# The DINOv3 ViT-S+/16 backbone (dinov3_vits16plus) in its ORIGINAL key format, as a --dino pointwise checkpoint
+# stores it under "dino." and the stand-alone pretrain file stores it without a prefix. This table is the whole
+# name mapping: role -> (original key, shape, synthetic init rule). The SwiGLU roles follow the published
+# SwiGLUFFN (w1 = gate, w2 = up, w3 = down); w3's shape confirms "down", the gate / up order does not show in
+# the shapes (DESIGN.md "DINOv3 backbone").
+DINO_PREFIX = "dino."
+DINO_TOP_KEYS = {
+    "cls_token": ("cls_token", (1, 1, arch.DINO_DIM), "token"),
+    "storage_tokens": ("storage_tokens", (1, arch.DINO_STORAGE, arch.DINO_DIM), "token"),
+    "mask_token": ("mask_token", (1, arch.DINO_DIM), "zeros"),          # unused at inference
+    "patch_w": ("patch_embed.proj.weight", (arch.DINO_DIM, 3, arch.DINO_PATCH, arch.DINO_PATCH), "lin_std"),
+    "patch_b": ("patch_embed.proj.bias", (arch.DINO_DIM,), "dino_bias"),
+    "rope_periods": ("rope_embed.periods", (arch.DINO_HEAD_DIM // 4,), "rope_periods"),
+    "norm_w": ("norm.weight", (arch.DINO_DIM,), "ln_gamma"),
+    "norm_b": ("norm.bias", (arch.DINO_DIM,), "ln_beta"),
+}
+DINO_BLOCK_KEYS = {
+    "ln1_w": ("norm1.weight", (arch.DINO_DIM,), "ln_gamma"),
+    "ln1_b": ("norm1.bias", (arch.DINO_DIM,), "ln_beta"),
+    "qkv_w": ("attn.qkv.weight", (3 * arch.DINO_DIM, arch.DINO_DIM), "lin_std"),
+    "qkv_b": ("attn.qkv.bias", (3 * arch.DINO_DIM,), "dino_bias"),
+    "qkv_mask": ("attn.qkv.bias_mask", (3 * arch.DINO_DIM,), "qkv_mask"),
+    "proj_w": ("attn.proj.weight", (arch.DINO_DIM, arch.DINO_DIM), "lin_std"),
+    "proj_b": ("attn.proj.bias", (arch.DINO_DIM,), "dino_bias"),
+    "ls1": ("ls1.gamma", (arch.DINO_DIM,), "layerscale"),
+    "ln2_w": ("norm2.weight", (arch.DINO_DIM,), "ln_gamma"),
+    "ln2_b": ("norm2.bias", (arch.DINO_DIM,), "ln_beta"),
+    "gate_w": ("mlp.w1.weight", (arch.DINO_HIDDEN, arch.DINO_DIM), "lin_std"),
+    "gate_b": ("mlp.w1.bias", (arch.DINO_HIDDEN,), "dino_bias"),
+    "up_w": ("mlp.w2.weight", (arch.DINO_HIDDEN, arch.DINO_DIM), "lin_std"),
+    "up_b": ("mlp.w2.bias", (arch.DINO_HIDDEN,), "dino_bias"),
+    "down_w": ("mlp.w3.weight", (arch.DINO_DIM, arch.DINO_HIDDEN), "lin_std"),
+    "down_b": ("mlp.w3.bias", (arch.DINO_DIM,), "dino_bias"),
+    "ls2": ("ls2.gamma", (arch.DINO_DIM,), "layerscale"),
+}
+# present in the published files, not required: without the mask the bias is used as stored, without the
+# periods they are computed (100^(k/16))
+DINO_OPTIONAL_ROLES = ("qkv_mask", "rope_periods", "mask_token")
+
+
+def dino_key(role: str, block: int = -1) -> str:
+    """The original state-dict key of a role of DINO_TOP_KEYS (block < 0) or DINO_BLOCK_KEYS."""
+    return DINO_TOP_KEYS[role][0] if block < 0 else f"blocks.{block}.{DINO_BLOCK_KEYS[role][0]}"
+
+
+def dino_manifest() -> List[Tuple[str, Tuple[int, ...], str]]:
+    out = [v for v in DINO_TOP_KEYS.values()]
+    for i in range(arch.DINO_BLOCKS):
+        out += [(f"blocks.{i}.{k}", s, r) for k, s, r in DINO_BLOCK_KEYS.values()]
+    return out
+
+
+def dino_optional_keys() -> List[str]:
+    out = [dino_key(r) for r in DINO_OPTIONAL_ROLES if r in DINO_TOP_KEYS]
+    for i in range(arch.DINO_BLOCKS):
+        out += [dino_key(r, i) for r in DINO_OPTIONAL_ROLES if r in DINO_BLOCK_KEYS]
+    return out
+
+
+def split_dino(sd: StateDict) -> Tuple[StateDict, StateDict]:
+    """(the state dict without its "dino." keys, those keys with the prefix removed)."""
+    rest = {k: v for k, v in sd.items() if not k.startswith(DINO_PREFIX)}
+    dino = {k[len(DINO_PREFIX):]: v for k, v in sd.items() if k.startswith(DINO_PREFIX)}
+    return rest, dino
+
+
+def round_bf16(x: np.ndarray) -> np.ndarray:
+    """float32 values rounded to the nearest bfloat16 (ties to even), as float32."""
+    u = np.ascontiguousarray(x, np.float32).view(np.uint32).astype(np.uint64)
+    u = (u + 0x7FFF + ((u >> 16) & 1)) & 0xFFFF0000
+    return u.astype(np.uint32).view(np.float32)
+
+
+def dino_rope_periods() -> np.ndarray:
+    """100^(4k/64), k < 16, in float64 (the published weights store these rounded through bf16)."""
+    return 100.0 ** (np.arange(arch.DINO_HEAD_DIM // 4, dtype=np.float64) * 4.0 / arch.DINO_HEAD_DIM)
+
+
 def manifest(kind: str) -> List[Tuple[str, Tuple[int, ...], str]]:
     """(key, shape, init rule) for every tensor of the model selected by ``kind``.
     ``*_pointwise``: the --dino pointwise model (Pointnet2ClsMSGFus encoder, ImgEncoder, the same heads;
     the frozen DINOv3 backbone ahead of the ImgEncoder is not part of it: its weights are absent,
     SURVEY §8c)."""
     out: List[Tuple[str, Tuple[int, ...], str]] = []
+    if kind == "dino":
+        return dino_manifest()
     if kind in ("score", "energy", "score_pointwise", "energy_pointwise"):
         out += fus_encoder_manifest() + img_encoder_manifest() if kind.endswith("_pointwise") \
             else _sa_manifest(arch.sa_branches())
@@ -164,13 +244,32 @@ def _draw(rng: np.random.Generator, shape, rule: str) -> np.ndarray:
         return rng.normal(0.0, 1.0, size=shape)
     if rule.startswith("const:"):  # nn.Parameter(torch.tensor(v))
         return np.full(shape, float(rule.split(":")[1]))
+    # the DINOv3 backbone's synthetic rules make attention position-sensitive (with the usual 0.02 init the
+    # softmax is flat and a RoPE mistake is invisible): q . k / 8 has unit spread
+    if rule == "lin_std":         # N(0, 1 / fan_in)
+        return rng.normal(0.0, 1.0 / np.sqrt(int(np.prod(shape[1:]))), size=shape)
+    if rule == "dino_bias":       # nonzero everywhere, the key bias included (the mask then matters)
+        return rng.normal(0.0, 0.5, size=shape)
+    if rule == "token":
+        return rng.normal(0.0, 1.0, size=shape)
+    if rule == "layerscale":
+        return rng.uniform(0.5, 1.5, size=shape)
+    if rule == "zeros":
+        return np.zeros(shape)
+    if rule == "qkv_mask":        # 1 for q and v, 0 for k
+        m = np.ones(shape)
+        m[shape[0] // 3: 2 * (shape[0] // 3)] = 0.0
+        return m
+    if rule == "rope_periods":
+        return round_bf16(dino_rope_periods().astype(np.float32))
     if rule == "gfp":             # GaussianFourierProjection: randn(64) * 30 (scorenet.py:84)
         return rng.normal(0.0, 1.0, size=shape) * arch.GFP_SCALE
     raise ValueError(rule)
 
 
 def synthetic_state_dict(kind: str, seed: int = 0) -> StateDict:
-    """Deterministic synthetic weights for ``kind`` (score | energy | scale)."""
+    """Deterministic synthetic weights for ``kind`` (score | energy | scale | *_pointwise | dino: the DINOv3
+    backbone in its original key format, without a prefix)."""
     sd: StateDict = {}
     for key, shape, rule in manifest(kind):
         if rule == "zero_i64":
@@ -197,13 +296,14 @@ def load_checkpoint(path: str) -> StateDict:
 def check_keys(sd: StateDict, kind: str) -> None:
     """Strict key/shape check, like ``load_state_dict(strict=True)``."""
     want = {k: s for k, s, _ in manifest(kind)}
-    missing = [k for k in want if k not in sd]
+    optional = set(dino_optional_keys()) if kind == "dino" else set()
+    missing = [k for k in want if k not in sd and k not in optional]
     unexpected = [k for k in sd if k not in want]
     if missing or unexpected:
         raise RuntimeError(f"Error(s) in loading state_dict: missing={missing[:5]} "
                            f"unexpected={unexpected[:5]}")
     for k, s in want.items():
-        if tuple(sd[k].shape) != tuple(s):
+        if k in sd and tuple(sd[k].shape) != tuple(s):
             raise RuntimeError(f"size mismatch for {k}: {tuple(sd[k].shape)} vs {s}")
 
 

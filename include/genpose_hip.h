@@ -135,7 +135,9 @@ int gp_linear(const float *x, int ldx, int m, int k, const float *w, const float
  * by the caller with flags |= GP_LINEAR_RMAX_GIVEN (e.g. the ymax of the linear that produced x).
  * ymax: NULL, or m floats that receive max |y| per row. act 3 is GatedAttentionFusion's gate with its
  * mix (attention.py:316-320): x = [cur | att] (k = 2n), y = g * cur + (1 - g) * att with
- * g = sigmoid(x W^T + b). */
+ * g = sigmoid(x W^T + b). act 4 adds into y (y += x W^T + b: a residual stream updated in place). act 5 is
+ * SwiGLU over output tiles paired (2t, 2t + 1) = (gate, up): y (m, n / 2) with
+ * y[:, 16t + c] = silu(z[:, 32t + c]) * z[:, 32t + 16 + c], z = x W^T + b; n % 32 == 0, ldy >= n / 2; ymax is y's. */
 #define GP_LINEAR_RMAX_GIVEN 1
 size_t gp_linear_split_words(int n, int k);
 int gp_linear_split(const float *x, int ldx, int m, int k, const int32_t *wpk, const float *bias, int n,
@@ -523,6 +525,54 @@ int gp_img_geo_table(const float *rel_pos_emb, int num_emb, int edim, int grid, 
  * the reference's patch_px = 14, grid = 16). feat (b, np, d), xs/ys (b, n) int32 -> out (b, n, d). */
 int gp_gather_patch_points(const float *feat, int b, int np, int d, const int *xs, const int *ys, int n,
                            int patch_px, int grid, float *out, hipStream_t stream);
+
+/* ===================================================================== DINOv3 ViT-S+/16 backbone
+ * get_intermediate_layers(rgb, n=out_layers, reshape=False, norm=True, return_class_token=False) of
+ * dinov3_vits16plus: D = 384, 12 blocks, 6 heads of 64, patch 16, 1 cls + 4 storage tokens, SwiGLU hidden 1536,
+ * LayerNorm eps 1e-5, RoPE on the patch tokens' q and k. All pointers are device pointers.
+ * LayerScale is folded into proj / w3 on the host, the qkv bias carries its mask (genpose2_amd/dino.py
+ * pack_dino). w12 is [w1 | w2] interleaved in 16-row tiles: rows 32t..32t+15 = w1 rows 16t.., rows
+ * 32t+16..32t+31 = w2 rows 16t.. (gate and up of one hidden unit meet in one lane of the SwiGLU epilogue).
+ * *_w: row-major fp32 (read by arith 1); *_h: the same matrix in pack_split_linear's layout (read by arith 0). */
+typedef struct {
+    const float *ln1_w, *ln1_b;
+    const float *qkv_w; /* (1152,384) */
+    const float *qkv_b; /* bias * bias_mask */
+    const float *proj_w; /* ls1 * W (384,384) */
+    const float *proj_b; /* ls1 * b */
+    const float *ln2_w, *ln2_b;
+    const float *w12_w; /* (3072,384), interleaved */
+    const float *w12_b;
+    const float *w3_w; /* ls2 * W (384,1536) */
+    const float *w3_b; /* ls2 * b */
+    const int32_t *qkv_h, *proj_h, *w12_h, *w3_h;
+} gp_dino_block;
+typedef struct {
+    const float *patch_w; /* (384,768), k = c * 256 + ky * 16 + kx */
+    const float *patch_b;
+    const float *cls_token; /* (384) */
+    const float *storage_tokens; /* (4,384) */
+    const float *norm_w, *norm_b;
+    const float *rope; /* gp_dino_rope_table's output for (rope_hp, rope_wp) */
+    int rope_hp, rope_wp;
+    gp_dino_block blocks[12];
+} gp_dino_weights;
+enum { GP_DINO_SPLIT_F16 = 0, GP_DINO_F32 = 1 };
+/* Bytes of gp_dino_forward's workspace for b images of h x w pixels: room for one chunk of
+ * min(b, max(1, 21760 / tokens)) images (0 for arguments gp_dino_forward rejects). */
+size_t gp_dino_workspace_size(int b, int h, int w);
+/* The RoPE table of an hp x wp patch grid -> table (hp * wp, 64) device floats, per patch [cos(32) | sin(32)]
+ * of the angles [h(16) | w(16)]: 2 pi * (2 (i + 0.5) / hp - 1) / periods[k]. periods_host: 16 HOST floats, or
+ * NULL for 100^(k/16). Evaluated in float64 on the host, rounded once, copied synchronously. */
+int gp_dino_rope_table(const float *periods_host, int hp, int wp, float *table, hipStream_t stream);
+/* rgb (b,3,h,w) -> outs[i] (b, hp * wp, 384) = norm(hidden state after block out_layers[i]) without the 5 prefix
+ * tokens, i < n_out; only max(out_layers) + 1 blocks run. h, w multiples of 16, hp * wp <= 1024, b >= 1. The batch
+ * is processed in chunks of as many images as the workspace holds (at least gp_dino_workspace_size(1, h, w) bytes;
+ * chunking does not change a bit of the result). arith: GP_DINO_SPLIT_F16 (the linears as gp_linear_split) or
+ * GP_DINO_F32 (gp_linear); the patch embedding and the attention are exact fp32 MFMA in both. */
+int gp_dino_forward(const gp_dino_weights *wt, const float *rgb, int b, int h, int w, int n_out,
+                    const int *out_layers, float *const *outs, int arith, void *workspace, size_t workspace_bytes,
+                    hipStream_t stream);
 
 /* ===================================================================== ScaleNet
  * ScaleNet.forward (scalenet.py:33-49): axes (b,3,3), pts_feat (b,1024) -> length (b,3). */
