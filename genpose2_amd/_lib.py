@@ -112,6 +112,10 @@ _SIGS: Dict[str, tuple] = {
     "gp_pc_sample": (c_int, [ctypes.POINTER(HeadWeights), c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int,
                              c_int, c_void_p, c_void_p, c_void_p, c_uint64, c_float, c_void_p, c_void_p, c_void_p,
                              c_void_p, c_size_t, c_void_p]),
+    "gp_pc_object_workspace_size": (c_size_t, [c_int]),
+    "gp_pc_sample_object": (c_int, [ctypes.POINTER(HeadWeights), c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int,
+                                    c_int, c_void_p, c_void_p, c_void_p, c_uint64, c_float, c_void_p, c_void_p,
+                                    c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p]),
     "gp_pc_global_partials": (c_int, [c_int, c_int, c_int, c_int]),
     "gp_pc_sample_global": (c_int, [ctypes.POINTER(HeadWeights), c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int,
                                     c_int, c_void_p, c_uint64, c_float, c_void_p, c_void_p, c_void_p, c_int, c_int,

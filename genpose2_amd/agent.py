@@ -56,6 +56,9 @@ class PoseNet:
         self._denoise_scalars = {}                 # ODE: (eps, steps) -> the denoise step's scalars
         self.global_batch = None                   # shard.GlobalBatch: this call is one shard of a global-batch
                                                    # PC / ODE call (runner.ShardedEvaluationPipeline(global_batch=True))
+        self.object_window = None                  # cfg.pc_coupling == "object": (objects in the whole batch, index
+                                                   # of this call's first object) when the call is a slice of a
+                                                   # larger batch; None: the call is the whole batch
         self._gen = torch.Generator(device=self.device)
         self._gen.manual_seed(self.cfg.noise_seed)
         self.weights_source = f"synthetic(seed={self.cfg.seed})"
@@ -243,6 +246,18 @@ class PoseNet:
                                       "drives the PC sampler only)")
         if energy_grad and self.global_batch is not None:
             raise NotImplementedError("global-batch sampling is not built for agent_type='energy'")
+        coupling = self.cfg.pc_coupling
+        if coupling == "object":
+            for bad, what in ((self.cfg.sampler_mode[0] == "ode", "the ODE sampler (one RK45 step controller per "
+                               "object is not built)"),
+                              (energy_grad, "agent_type='energy'"),
+                              (bool(return_average_res), "return_average_res"),
+                              (self.global_batch is not None, "global-batch sampling (set object_window instead: "
+                               "per-object rows need no exchange)")):
+                if bad:
+                    raise NotImplementedError(f"pc_coupling='object' is not built for {what}")
+        elif self.object_window is not None:
+            raise ValueError("object_window belongs to pc_coupling='object'")
         self.is_testing = True
         feat = self._encode(data) if extract_feature else dev.require_device_tensor(data["pts_feat"], "pts_feat")
         data["pts_feat"] = feat
@@ -262,7 +277,15 @@ class PoseNet:
             T = int(self.cfg.sampling_steps)
             tab, tproj = self._pc_table(T)
             gb = self.global_batch
-            if rep_init is None and gb is not None:   # this shard's rows of the whole batch's prior draw
+            rows_total, row_off = None, 0
+            if coupling == "object" and self.object_window is not None:
+                total, first = (int(v) for v in self.object_window)
+                if not 0 <= first <= total - bs:
+                    raise ValueError(f"object_window: objects [{first}, {first + bs}) outside a batch of {total}")
+                rows_total, row_off = total * K, first * K
+            if rep_init is None and rows_total is not None:   # this window's rows of the whole batch's prior draw
+                x = (self._draw_prior(rows_total)[row_off:row_off + R] * sde.prior_sigma(arch.SDE_T)).contiguous()
+            elif rep_init is None and gb is not None:   # this shard's rows of the whole batch's prior draw
                 if self.noise_feed is not None:
                     raise ValueError("global-batch sampling draws the prior itself (noise_feed not supported)")
                 x = (self._draw_prior(gb.total * K)[gb.lo * K:gb.hi * K] * sde.prior_sigma(arch.SDE_T)).contiguous()
@@ -277,7 +300,8 @@ class PoseNet:
             seed = (self.cfg.noise_seed * 1000003 + self._calls) & 0xFFFFFFFFFFFF
             want_xs = bool(return_process or self.cfg.save_video)
             res, q, xs = self.heads.pc_sample(pobj, tproj, tab, x, K, center, z1, z2, seed=seed, want_xs=want_xs,
-                                              global_batch=gb, energy_grad=energy_grad)
+                                              global_batch=gb, energy_grad=energy_grad, coupling=coupling,
+                                              rows_total=rows_total, row_off=row_off)
             pred_pose = res.view(bs, K, -1)
             pred_q = q.view(bs, K, -1)
             in_process = xs.view(bs, K, T, -1) if xs is not None else None

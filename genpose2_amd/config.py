@@ -45,6 +45,10 @@ class GenPoseConfig:
     # build-specific knobs (no reference counterpart)
     noise: str = "philox"                  # philox (device RNG) | injected (parity buffers)
     noise_seed: int = 0
+    # what the PC corrector's step size averages the score norm over: batch (every row of the call, the
+    # reference's cond_pc_sampler as evaluation calls it) | object (each object's own candidates: a pose then
+    # does not depend on which other objects share the call; DESIGN "Per-object coupling")
+    pc_coupling: str = "batch"
 
     def copy(self, **kw) -> "GenPoseConfig":
         return replace(self, **kw)
@@ -70,3 +74,5 @@ class GenPoseConfig:
             raise NotImplementedError("only the IP/score/identical energy is built")
         if self.noise not in ("philox", "injected"):
             raise ValueError(f"noise {self.noise}")
+        if self.pc_coupling not in ("batch", "object"):
+            raise ValueError(f"pc_coupling {self.pc_coupling!r} (batch | object)")

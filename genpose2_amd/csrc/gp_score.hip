@@ -312,15 +312,44 @@ struct PCArgs {
 struct PCArgsGrad : PCArgs {
     gp_head_grad_weights gw;
 };
+// The per-object step's arguments (gp_pc_sample_object): the same, plus the row norms that take the place of the
+// per-workgroup partials. A type of its own for the same reason.
+struct PCArgsObj : PCArgs {
+    float* rnorm;         // (2, R) ||s_r|| of every row of the call: launch i writes slot i&1 and reads the other
+};
+
+// grad_norm of the object that row r of the call belongs to (OBJ step): the mean of its kper rows' score norms in
+// `rn` (one slot of PCArgsObj::rnorm). The order of the sum is a function of j and kper alone -- not of the tile,
+// the lane's place in the workgroup, rows or row_off -- so an object's step size has the same bits whatever else
+// the call holds: the row's four lanes p = 0..3 each run the chain of j = p, p+4, p+8, .. < kper in increasing
+// j from 0.f (c_p), and the chains combine as (c0 + c1) + (c2 + c3) by two quad DPP adds, which leave the same
+// bits in all four lanes (fp32 addition commutes). Four loads in flight per lane and pass; an index past the
+// object reads its last row and adds +0.f instead, which changes no bit of a non-negative sum.
+__device__ __forceinline__ float pc_object_grad_norm(const float* rn, int r, int kper, int p) {
+#pragma clang fp contract(off)
+    const float* o = rn + (size_t)(r / kper) * kper;
+    float c = 0.f;
+    for (int j = p; j < kper; j += 16) {
+        float v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) v[u] = ld1(o + min(j + 4 * u, kper - 1));
+#pragma unroll
+        for (int u = 0; u < 4; ++u) c += j + 4 * u < kper ? v[u] : 0.f;
+    }
+    c = dpp_add<0xB1>(c);          // quad_perm [1,0,3,2]: c0 + c1 | c2 + c3
+    c = dpp_add<0x4E>(c);          // quad_perm [2,3,0,1]: (c0 + c1) + (c2 + c3)
+    return fdiv(c, (float)kper);
+}
 
 // One update wave's part of step i-1 -> i for its 16 rows (wave g owns rows 16g .. 16g+15, four lanes per row:
 // part p < 3 owns elements [3p, 3p+3) -- rot6 columns a1, a2, translation; lane 4c+3 only pads the row).
 // gacc: the lane's share of sum_r ||s_r|| over every row of step i-1, summed by the caller in the fixed
-// lane / index order both kernels share, so every workgroup derives the identical grad_norm. x3: this lane's
+// lane / index order both kernels share, so every workgroup derives the identical grad_norm (OBJ: the row's
+// grad_norm itself, pc_object_grad_norm). x3: this lane's
 // entries of x (updated in place); sv, z1v, z2v: its entries of the previous score and the two draws.
 // Writes xin (the trunk's input), the split trunk's per-column scales, obj, and the outputs (x when store_x,
 // the trajectory, res / q at the last step).
-template <int NT, int WV, int PL>
+template <int NT, int WV, int PL, bool OBJ = false>
 __device__ __forceinline__ void pc_update_rows(const PCArgs& a, int i, const PCStep& prev, HeadSmem<NT, WV, PL>& sm,
                                                int* obj, int g, int lane, int r0, float gacc, float (&x3)[3],
                                                const float (&sv)[3], const float (&z1v)[3], const float (&z2v)[3],
@@ -334,13 +363,13 @@ __device__ __forceinline__ void pc_update_rows(const PCArgs& a, int i, const PCS
         obj[16 * g + lane] = (r < a.rows ? r : a.rows - 1) / a.kper;
     }
     PC_MARK(10);
-    gacc = wave_sum(gacc);
+    if constexpr (!OBJ) gacc = wave_sum(gacc);
     PC_MARK(11);
     const int c = 16 * g + (lane >> 2);
     const int r = r0 + c;
     const bool upd = i > 0 && r < a.rows && p < 3;
     if (upd) {
-        const float gn = fdiv(gacc, (float)a.norm_rows);
+        const float gn = OBJ ? gacc : fdiv(gacc, (float)a.norm_rows);
         const float ratio = fdiv(a.ls_coef, gn);
         const float ls = 2.0f * (ratio * ratio);
         const float sq2ls = sqrtf(2.0f * ls);
@@ -452,9 +481,11 @@ __device__ __forceinline__ void pc_make_draws(const PCArgs& a, int i, int r0, Ds
 // s = f / (sigma + 1e-7) for the workgroup's rows (a lane per (row, output): 4 rows per wave as 16-lane rows,
 // outputs 0..8 valid, row norms by a DPP row sum) handed to put(c, o, s); the waves' partials of sum_r ||s_r||
 // combined in wave order after one barrier. Returns the workgroup partial (valid in thread 0).
-template <int NT, int WV, int PL, typename Put>
+// OBJ (the per-object step): each row's norm goes to rnorm[r] from the row's first lane instead, and there is
+// no workgroup partial (and no barrier).
+template <int NT, int WV, int PL, bool OBJ = false, typename Put>
 __device__ __forceinline__ float pc_score_norm(const PCArgs& a, const PCStep& cur, HeadSmem<NT, WV, PL>& sm, int r0,
-                                               int wid, int lane, Put put) {
+                                               int wid, int lane, Put put, float* rnorm = nullptr) {
     constexpr int ROWS = NT * 16;
     const float den = fadd(cur.sigma, 1e-7f);
     float wsum = 0.f;
@@ -466,8 +497,14 @@ __device__ __forceinline__ float pc_score_norm(const PCArgs& a, const PCStep& cu
             v = fdiv(head_out(sm, c, o), den);
             put(c, o, v);
         }
-        wsum += rows_sum(sqrtf(row16_sum(fmul(v, v))));
+        const float n = sqrtf(row16_sum(fmul(v, v)));
+        if constexpr (OBJ) {
+            if (o == 0 && r < a.rows) rnorm[r] = n;
+        } else {
+            wsum += rows_sum(n);
+        }
     }
+    if constexpr (OBJ) return 0.f;
     if (lane == 0) sm.scratch[wid] = wsum;
     __syncthreads();
     float t = 0.f;
@@ -513,12 +550,17 @@ __device__ __forceinline__ float pc_energy_score_norm(const PCArgs& a, const PCS
 // GRAD: the score is the energy model's, f / sigma + J_f^T (x / sigma) (the trunk's gradient form and
 // head_backward, gp_head.h) on the transposed weights of PCArgsGrad; update waves, draws, partial slots and the
 // finalize launch are the same.
-template <int NT, int WV, int PL, bool GRAD = false>   // PL 0: exact fp32 GEMMs, X3P: f16x3
-__global__ __launch_bounds__(WV * 64) void pc_step_kernel(std::conditional_t<GRAD, PCArgsGrad, PCArgs> a, int i,
-                                                          PCStep cur, PCStep prev) {
+// OBJ: the per-object step (gp_pc_sample_object). The scoring side stores every row's ||s_r|| (PCArgsObj::rnorm)
+// and writes no workgroup partial; an update lane forms the grad_norm of its row's object alone from them
+// (pc_object_grad_norm, which fixes the order of that sum). Everything after grad_norm is the same code.
+template <bool GRAD, bool OBJ>
+using PCArgsOf = std::conditional_t<GRAD, PCArgsGrad, std::conditional_t<OBJ, PCArgsObj, PCArgs>>;
+template <int NT, int WV, int PL, bool GRAD = false, bool OBJ = false>   // PL 0: exact fp32 GEMMs, X3P: f16x3
+__global__ __launch_bounds__(WV * 64) void pc_step_kernel(PCArgsOf<GRAD, OBJ> a, int i, PCStep cur, PCStep prev) {
     constexpr int ROWS = NT * 16;
     static_assert(NT < WV, "at least one wave besides the update waves");
     static_assert(!GRAD || (NT == 1 && PL == 0), "the energy gradient runs the exact-fp32 16-candidate tile");
+    static_assert(!(GRAD && OBJ), "the energy gradient has no per-object step");
     __shared__ HeadSmem<NT, WV, PL> sm;
     __shared__ int obj[ROWS];
     const int tid = threadIdx.x;
@@ -539,8 +581,10 @@ __global__ __launch_bounds__(WV * 64) void pc_step_kernel(std::conditional_t<GRA
         const float* z2p = inj ? a.z2 + ((size_t)(i > 0 ? i - 1 : 0) * a.rows) * 9 : zslot + (size_t)a.rows * 9;
         const float* part = a.part + (size_t)((i - 1) & 1) * a.part_n;
         float pv[8];
+        if constexpr (!OBJ) {
 #pragma unroll
-        for (int u = 0; u < 8; ++u) pv[u] = part[min(lane + 64 * u, a.part_n - 1)];
+            for (int u = 0; u < 8; ++u) pv[u] = part[min(lane + 64 * u, a.part_n - 1)];
+        }
         const int p = lane & 3;
         const int e0 = 3 * (p < 3 ? p : 0);
         float x3[3], sv[3], z1v[3], z2v[3];
@@ -556,16 +600,21 @@ __global__ __launch_bounds__(WV * 64) void pc_step_kernel(std::conditional_t<GRA
         }
         // grad_norm = mean_r ||s_r|| over all rows of step i-1 (samplers.py:143); unused at i=0
         float gacc = 0.f;
+        if constexpr (OBJ) {   // the mean over the rows of this row's object only, in pc_object_grad_norm's order
+            gacc = pc_object_grad_norm(a.rnorm + (size_t)((i - 1) & 1) * a.rows,
+                                       min(r0 + 16 * g + (lane >> 2), a.rows - 1), a.kper, p);
+        } else {
 #pragma unroll
-        for (int u = 0; u < 8; ++u) gacc += lane + 64 * u < a.part_n ? pv[u] : 0.f;
-        for (int t0 = 512; t0 < a.part_n; t0 += 512) {
+            for (int u = 0; u < 8; ++u) gacc += lane + 64 * u < a.part_n ? pv[u] : 0.f;
+            for (int t0 = 512; t0 < a.part_n; t0 += 512) {
 #pragma unroll
-            for (int u = 0; u < 8; ++u) pv[u] = part[min(t0 + lane + 64 * u, a.part_n - 1)];
+                for (int u = 0; u < 8; ++u) pv[u] = part[min(t0 + lane + 64 * u, a.part_n - 1)];
 #pragma unroll
-            for (int u = 0; u < 8; ++u) gacc += t0 + lane + 64 * u < a.part_n ? pv[u] : 0.f;
+                for (int u = 0; u < 8; ++u) gacc += t0 + lane + 64 * u < a.part_n ? pv[u] : 0.f;
+            }
         }
         PC_MARK(9);
-        pc_update_rows<NT, WV, PL>(a, i, prev, sm, obj, g, lane, r0, gacc, x3, sv, z1v, z2v, hs, true, trace_slot);
+        pc_update_rows<NT, WV, PL, OBJ>(a, i, prev, sm, obj, g, lane, r0, gacc, x3, sv, z1v, z2v, hs, true, trace_slot);
         PC_MARK(12);
     }
     if (i == a.steps) return;  // finalize launch: no score evaluation
@@ -586,9 +635,12 @@ __global__ __launch_bounds__(WV * 64) void pc_step_kernel(std::conditional_t<GRA
     } else {
         run_head_trunk<true>(a.w, a.pobj, a.tproj + (size_t)i * 768, obj, sm, trace_slot, hs);
         PC_MARK(7);
-        const float t = pc_score_norm<NT, WV, PL>(a, cur, sm, r0, wid, lane,
-                                                  [&](int c, int o, float v) { a.s[(size_t)(r0 + c) * 9 + o] = v; });
-        if (tid == 0) a.part[(size_t)(i & 1) * a.part_n + a.part_off + blockIdx.x] = t;
+        float* rnorm = nullptr;
+        if constexpr (OBJ) rnorm = a.rnorm + (size_t)(i & 1) * a.rows;
+        const float t = pc_score_norm<NT, WV, PL, OBJ>(
+            a, cur, sm, r0, wid, lane, [&](int c, int o, float v) { a.s[(size_t)(r0 + c) * 9 + o] = v; }, rnorm);
+        if constexpr (!OBJ)
+            if (tid == 0) a.part[(size_t)(i & 1) * a.part_n + a.part_off + blockIdx.x] = t;
         PC_MARK(8);
     }
 }
@@ -614,6 +666,11 @@ extern "C" int gp_randn(uint64_t seed, uint32_t stream, int rows, int cols, floa
     const long long n = (long long)rows * ((cols + 3) >> 2);
     hipLaunchKernelGGL(randn_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, hs, seed, stream, rows, cols, out);
     return gp_check_launch("randn_kernel");
+}
+
+extern "C" size_t gp_pc_object_workspace_size(int rows) {
+    // s (R,9) | row score norms (2, R) | Philox draws (2 slots, 2 streams, R, 9)
+    return sizeof(float) * ((size_t)rows * 9 * 5 + 2 * (size_t)rows) + 256;
 }
 
 extern "C" size_t gp_pc_workspace_size(int rows) {
@@ -660,31 +717,36 @@ extern "C" int gp_pc_step_table(int steps, float eps, float* out) {
 }
 
 // The shared body of gp_pc_sample and gp_pc_sample_global: nt column tiles per workgroup, grad_norm over
-// part_n partials of `part` averaged over norm_rows, exchange (if any) after every scoring launch.
+// part_n partials of `part` averaged over norm_rows, exchange (if any) after every scoring launch. object: the
+// per-object step (gp_pc_sample_object), whose row norms take the partials' place in the workspace.
 static int pc_sample_impl(const gp_head_weights* w, const float* pobj, const float* tproj, const float* step_tab,
                           int steps, float* x, int rows, int k, const float* pts_center, const float* z1,
                           const float* z2, uint64_t seed, float snr, float* res, float* q, float* xs, void* workspace,
                           size_t workspace_bytes, int nt, float* part, int part_n, int part_off, int norm_rows,
                           int row_off, gp_pc_exchange_fn exchange, void* ctx, hipStream_t stream,
-                          const gp_head_grad_weights* gw = nullptr) {
+                          const gp_head_grad_weights* gw = nullptr, bool object = false) {
     GP_REQUIRE(w && pobj && tproj && step_tab && x && pts_center && res && q && workspace,
                "pc_sample: null pointer");
     GP_REQUIRE(steps >= 2 && rows >= 1 && k >= 1, "pc_sample: need steps>=2, rows>=1, k>=1");
     GP_REQUIRE((z1 == nullptr) == (z2 == nullptr), "pc_sample: z1/z2 must both be given or both null");
-    GP_REQUIRE(workspace_bytes >= gp_pc_workspace_size(rows), "pc_sample: workspace too small");
+    GP_REQUIRE(workspace_bytes >= (object ? gp_pc_object_workspace_size(rows) : gp_pc_workspace_size(rows)),
+               "pc_sample: workspace too small");
     // split-f16 GEMMs when the packed planes are given (gp_head_weights), exact fp32 otherwise
     const bool split = w->pe2_h != nullptr;
     GP_REQUIRE(!split || (w->h1p_h && w->hsc), "pc_sample: pe2_h, h1p_h and hsc must be given together");
     // the hybrid form (three smallest products on block-scaled FP8 MFMA) when the e4m3 planes are given too
     GP_REQUIRE((w->pe2_q != nullptr) == (w->h1p_q != nullptr), "pc_sample: pe2_q and h1p_q must be given together");
-    const bool q8 = split && gw == nullptr && w->pe2_q != nullptr && (nt == 4 || (w->q8_flags & GP_Q8_ALL_TILES));
+    // (the per-object step keeps the six f16 products at every width)
+    const bool q8 = split && gw == nullptr && !object && w->pe2_q != nullptr &&
+                    (nt == 4 || (w->q8_flags & GP_Q8_ALL_TILES));
     PCArgs a;
     a.w = *w;
     a.pobj = pobj;
     a.tproj = tproj;
     a.x = x;
     a.s = static_cast<float*>(workspace);
-    a.zbuf = a.s + (size_t)rows * 9 + 2 * (((size_t)rows + 15) / 16);
+    // after s: the grad-norm partials (2, ntiles), or the per-object step's row norms (2, rows)
+    a.zbuf = a.s + (size_t)rows * 9 + 2 * (object ? (size_t)rows : ((size_t)rows + 15) / 16);
     a.z1 = z1;
     a.z2 = z2;
     a.seed = seed;
@@ -717,6 +779,15 @@ static int pc_sample_impl(const gp_head_weights* w, const float* pobj, const flo
             static_cast<PCArgs&>(ag) = a;
             ag.gw = *gw;
             hipLaunchKernelGGL((pc_step_kernel<1, PC_WV1, 0, true>), grid, dim3(PC_WV1 * 64), 0, stream, ag, i, cur, prev);
+        }
+        else if (object) {
+            PCArgsObj ao;
+            static_cast<PCArgs&>(ao) = a;
+            ao.rnorm = a.s + (size_t)rows * 9;
+            head_dispatch<4>(split ? X3P : 0, nt, [&](auto pl, auto ntc) {
+                hipLaunchKernelGGL((pc_step_kernel<ntc.value, PC_WV1, pl.value, false, true>), grid, dim3(PC_WV1 * 64), 0,
+                                   stream, ao, i, cur, prev);
+            });
         }
         else
             head_dispatch<4, true>(q8 ? X3Q : (split ? X3P : 0), nt, [&](auto pl, auto ntc) {
@@ -751,6 +822,24 @@ extern "C" int gp_pc_sample_energy(const gp_head_weights* w, const gp_head_grad_
     GP_REQUIRE(w != nullptr && grad_weights_ok(gw), "pc_sample_energy: null pointer");
     return pc_sample_impl(w, pobj, tproj, step_tab, steps, x, rows, k, pts_center, z1, z2, seed, snr, res, q, xs,
                           workspace, workspace_bytes, 1, nullptr, 0, 0, rows, 0, nullptr, nullptr, stream, gw);
+}
+
+// The PC sampler with the corrector's step size per object (genpose_hip.h): grad_norm of a row is the mean score
+// norm over its own object's k rows, summed in pc_object_grad_norm's order, so nothing a row computes depends on
+// the other objects of the call. The tile class follows rows_total, the Philox rows row_off + r.
+extern "C" int gp_pc_sample_object(const gp_head_weights* w, const float* pobj, const float* tproj,
+                                   const float* step_tab, int steps, float* x, int rows, int k,
+                                   const float* pts_center, const float* z1, const float* z2, uint64_t seed,
+                                   float snr, float* res, float* q, float* xs, int rows_total, int row_off,
+                                   void* workspace, size_t workspace_bytes, hipStream_t stream) {
+    GP_REQUIRE(w != nullptr, "pc_sample_object: null pointer");
+    GP_REQUIRE(rows >= 1 && k >= 1 && rows % k == 0, "pc_sample_object: %d rows are not whole objects of %d", rows, k);
+    GP_REQUIRE(row_off >= 0 && row_off % k == 0, "pc_sample_object: row_off %d is not a multiple of k = %d", row_off, k);
+    GP_REQUIRE(rows_total >= rows && row_off <= rows_total - rows,
+               "pc_sample_object: rows [%d, %d) outside rows_total = %d", row_off, row_off + rows, rows_total);
+    return pc_sample_impl(w, pobj, tproj, step_tab, steps, x, rows, k, pts_center, z1, z2, seed, snr, res, q, xs,
+                          workspace, workspace_bytes, head_pick_nt(rows_total, w->pe2_h != nullptr), nullptr, 0, 0,
+                          rows, row_off, nullptr, nullptr, stream, nullptr, true);
 }
 
 extern "C" int gp_pc_global_partials(int rows_total, int shard_rows_max, int shards, int split) {

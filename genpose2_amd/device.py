@@ -346,14 +346,30 @@ class HeadModel:
 
     def pc_sample(self, pobj, tproj, step_tab: np.ndarray, x: torch.Tensor, k: int, pts_center: torch.Tensor,
                   z1=None, z2=None, seed: int = 0, snr: float = arch.SNR, want_xs: bool = False, global_batch=None,
-                  energy_grad: bool = False):
+                  energy_grad: bool = False, coupling: str = "batch", rows_total=None, row_off: int = 0):
         """gp_pc_sample; with ``global_batch`` (shard.GlobalBatch) gp_pc_sample_global: this rank's rows of one
         call on the whole batch (grad_norm over every shard's rows, one partials all-gather per step).
-        ``energy_grad``: gp_pc_sample_energy, the sampler driven by the energy model's score (energy_score)."""
+        ``energy_grad``: gp_pc_sample_energy, the sampler driven by the energy model's score (energy_score).
+        ``coupling="object"``: gp_pc_sample_object, the corrector's step size from each object's own k rows, so an
+        object's result does not depend on the other objects of the call; the rows are rows [row_off, row_off + R)
+        of a batch of ``rows_total`` rows (default R: the call is the whole batch), which picks the tile class
+        and keys the device draws."""
+        if coupling not in ("batch", "object"):
+            raise ValueError(f"coupling {coupling!r} (batch | object)")
         if energy_grad and global_batch is not None:
             raise NotImplementedError("the energy-gradient sampler has no global-batch mode")
         R = x.shape[0]
         T = step_tab.shape[0]
+        if coupling == "object":
+            if energy_grad:
+                raise NotImplementedError("coupling='object' is not built for the energy-gradient sampler")
+            if global_batch is not None:
+                raise NotImplementedError("coupling='object' needs no global batch: its rows are independent of the "
+                                          "other shards' (pass rows_total / row_off instead)")
+            return self._pc_sample_object(pobj, tproj, step_tab, x, k, pts_center, z1, z2, seed, snr, want_xs,
+                                          R if rows_total is None else int(rows_total), int(row_off))
+        if rows_total is not None or row_off:
+            raise ValueError("rows_total / row_off belong to coupling='object' (global_batch carries the batch's)")
         need = int(self.lib.gp_pc_workspace_size(R))
         if self._pc_ws is None or self._pc_ws.numel() < need:
             self._pc_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
@@ -399,6 +415,26 @@ class HeadModel:
             ctypes.c_uint64(seed), ctypes.c_float(snr), ctypes.c_void_p(res.data_ptr()),
             ctypes.c_void_p(q.data_ptr()), ctypes.c_void_p(_ptr(xs)), ctypes.c_void_p(self._pc_ws.data_ptr()),
             self._pc_ws.numel(), self._s()), "pc_sample")
+        return res, q, xs
+
+    def _pc_sample_object(self, pobj, tproj, step_tab, x, k, pts_center, z1, z2, seed, snr, want_xs, rows_total,
+                          row_off):
+        R = x.shape[0]
+        T = step_tab.shape[0]
+        need = int(self.lib.gp_pc_object_workspace_size(R))
+        if self._pc_ws is None or self._pc_ws.numel() < need:
+            self._pc_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        res = torch.empty((R, 9), dtype=torch.float32, device=self.device)
+        q = torch.empty((R, 7), dtype=torch.float32, device=self.device)
+        xs = torch.empty((R, T, 9), dtype=torch.float32, device=self.device) if want_xs else None
+        tab = np.ascontiguousarray(step_tab, np.float32)
+        check(self.lib.gp_pc_sample_object(
+            ctypes.byref(self.w), ctypes.c_void_p(pobj.data_ptr()), ctypes.c_void_p(tproj.data_ptr()),
+            tab.ctypes.data_as(ctypes.c_void_p), T, ctypes.c_void_p(x.data_ptr()), R, k,
+            ctypes.c_void_p(pts_center.data_ptr()), ctypes.c_void_p(_ptr(z1)), ctypes.c_void_p(_ptr(z2)),
+            ctypes.c_uint64(seed), ctypes.c_float(snr), ctypes.c_void_p(res.data_ptr()),
+            ctypes.c_void_p(q.data_ptr()), ctypes.c_void_p(_ptr(xs)), rows_total, row_off,
+            ctypes.c_void_p(self._pc_ws.data_ptr()), self._pc_ws.numel(), self._s()), "pc_sample_object")
         return res, q, xs
 
 

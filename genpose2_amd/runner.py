@@ -142,13 +142,20 @@ class ShardedEvaluationPipeline:
     (shard.GlobalBatch): the PC sampler's Langevin grad_norm over every shard's rows (one all-gather of the
     score-norm partials per step) with the prior and device noise drawn for the whole batch; the ODE sampler's
     select_initial_step norms over the whole batch's state (three one-time all-gathers) and every RK45
-    attempt's error norm over every shard's partials (one all-gather per attempt)."""
+    attempt's error norm over every shard's partials (one all-gather per attempt).
+    ``cfg.pc_coupling == "object"`` needs none of that: every rank's score agent gets its shard as
+    ``object_window``, so its rows run the whole batch's tile class, prior rows and device draws, and each object's
+    poses are bit for bit those of one call on the whole batch, with no collective on the sampling path
+    (``global_batch=True`` is refused with it)."""
 
     def __init__(self, cfg: GenPoseConfig, with_energy: bool = True, with_scale: bool = False, src: int = 0,
                  global_batch: bool = False):
         self.local = EvaluationPipeline(cfg, with_energy, with_scale)
         self.src = src
         self.global_batch = global_batch
+        if global_batch and self.local.cfg.pc_coupling == "object":
+            raise NotImplementedError("pc_coupling='object' needs no global batch: a shard's objects do not depend "
+                                      "on the other shards'")
         self.sync_weights()
 
     def agents(self):
@@ -188,12 +195,15 @@ class ShardedEvaluationPipeline:
         if self.global_batch:
             self.local.score_agent.global_batch = shard.GlobalBatch.of(total)   # raises on an empty shard
         if hi > lo:
+            if self.local.cfg.pc_coupling == "object":
+                self.local.score_agent.object_window = (total, lo)
             # per-object tensors, and lists of them (the DINOv3 layers of --dino pointwise)
             try:
                 out = self.local.run({k: [t[lo:hi] for t in v] if isinstance(v, (list, tuple)) else v[lo:hi]
                                       for k, v in batch.items()})
             finally:
                 self.local.score_agent.global_batch = None
+                self.local.score_agent.object_window = None
         else:   # more ranks than objects: an empty shard still joins the gathers
             d = batch["pts"].device
             z = lambda *s: torch.zeros(s, dtype=torch.float32, device=d)  # noqa: E731

@@ -328,6 +328,30 @@ int gp_pc_sample_global(const gp_head_weights *w, const float *pobj, const float
                         int shard_rows_max, float *part, gp_pc_exchange_fn exchange, void *ctx,
                         void *workspace, size_t workspace_bytes, hipStream_t stream);
 
+/* Per-object PC sampling: cond_pc_sampler as the reference runs it when called once per object on that
+ * object's k candidates. The Langevin step size of a row comes from the mean score norm of its own object's k
+ * rows, gn_b = (sum_{j<k} ||s_{b*k+j}||) / k, in place of the mean over every row of the call; nothing else
+ * differs from gp_pc_sample. The order of that sum is a function of j and k alone: four chains c_p, p = 0..3,
+ * each adding the rows j = p, p+4, p+8, ... in increasing j from 0, combined as (c0 + c1) + (c2 + c3).
+ * rows (this call's, whole objects: a multiple of k) are rows [row_off, row_off + rows) of a batch of rows_total
+ * rows (row_off a multiple of k, rows_total >= row_off + rows): rows_total selects the tile class
+ * (gp_pc_tile_rows(rows_total, split)), so a slice of a large batch runs the large batch's arithmetic, and the
+ * Philox draws are keyed by the global row row_off + r. pobj, x, pts_center, the outputs and injected z1 / z2
+ * (T, rows, 9) hold this call's objects and rows only. With the f16x3 planes given the step runs the f16x3 trunk
+ * at every tile class (the e4m3 planes are not used).
+ * Contract: an object's res, q, x and xs rows are bit-identical for any set of other objects in the call and for
+ * any split of a batch into calls, given the same rows_total, the same global row index of its rows (Philox
+ * draws; any row_off with injected noise) and the same arithmetic (weights, planes, seed, snr, step_tab).
+ * workspace: gp_pc_object_workspace_size(rows) bytes; no allocation in the call. Bad arguments return a status
+ * and set gp_last_error() before anything is launched. */
+size_t gp_pc_object_workspace_size(int rows);
+int gp_pc_sample_object(const gp_head_weights *w, const float *pobj, const float *tproj,
+                        const float *step_tab, int steps, float *x, int rows, int k,
+                        const float *pts_center, const float *z1, const float *z2, uint64_t seed,
+                        float snr, float *res, float *q, float *xs,
+                        int rows_total, int row_off,
+                        void *workspace, size_t workspace_bytes, hipStream_t stream);
+
 /* The step table of cond_pc_sampler (samplers.py:129-130, sde.py:15-27) for hosts without Python:
  * out (HOST, steps x 5 fp32) = {t, sigma(t), g(t), dt, sqrt(dt)} with t = torch.linspace(1, eps,
  * steps) in float32 (bit-identical to torch's CPU rounding), sigma = f32(0.01) * 5000^t (power
