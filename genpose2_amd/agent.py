@@ -56,9 +56,11 @@ class PoseNet:
         self._denoise_scalars = {}                 # ODE: (eps, steps) -> the denoise step's scalars
         self.global_batch = None                   # shard.GlobalBatch: this call is one shard of a global-batch
                                                    # PC / ODE call (runner.ShardedEvaluationPipeline(global_batch=True))
-        self.object_window = None                  # cfg.pc_coupling == "object": (objects in the whole batch, index
-                                                   # of this call's first object) when the call is a slice of a
-                                                   # larger batch; None: the call is the whole batch
+        self.last_nfev_objects = self.last_status_objects = None   # ODE, cfg.ode_coupling == "object": per object
+        self.object_window = None                  # pc_coupling / ode_coupling == "object" (the sampler in use's):
+                                                   # (objects in the whole batch, index of this call's first
+                                                   # object) when the call is a slice of a larger batch; None:
+                                                   # the call is the whole batch
         self._gen = torch.Generator(device=self.device)
         self._gen.manual_seed(self.cfg.noise_seed)
         self.weights_source = f"synthetic(seed={self.cfg.seed})"
@@ -247,17 +249,28 @@ class PoseNet:
         if energy_grad and self.global_batch is not None:
             raise NotImplementedError("global-batch sampling is not built for agent_type='energy'")
         coupling = self.cfg.pc_coupling
+        ode_object = self.cfg.sampler_mode[0] == "ode" and self.cfg.ode_coupling == "object"
         if coupling == "object":
-            for bad, what in ((self.cfg.sampler_mode[0] == "ode", "the ODE sampler (one RK45 step controller per "
-                               "object is not built)"),
+            for bad, what in ((self.cfg.sampler_mode[0] == "ode", "the ODE sampler (its per-object mode is "
+                               "ode_coupling='object')"),
                               (energy_grad, "agent_type='energy'"),
                               (bool(return_average_res), "return_average_res"),
                               (self.global_batch is not None, "global-batch sampling (set object_window instead: "
                                "per-object rows need no exchange)")):
                 if bad:
                     raise NotImplementedError(f"pc_coupling='object' is not built for {what}")
+        elif ode_object:
+            for bad, what in ((bool(return_process or self.cfg.save_video), "return_process / save_video"),
+                              (self.ode_host_control or self.ode_trace is not None, "ode_host_control / ode_trace "
+                               "(the host controller and its trajectory are whole-batch)"),
+                              (bool(return_average_res), "return_average_res"),
+                              (self.global_batch is not None, "global-batch sampling (set object_window instead: "
+                               "per-object solves need no exchange)")):
+                if bad:
+                    raise NotImplementedError(f"ode_coupling='object' is not built for {what}")
         elif self.object_window is not None:
-            raise ValueError("object_window belongs to pc_coupling='object'")
+            raise ValueError("object_window belongs to pc_coupling='object' (PC sampler) or ode_coupling='object' "
+                             "(ODE sampler)")
         self.is_testing = True
         feat = self._encode(data) if extract_feature else dev.require_device_tensor(data["pts_feat"], "pts_feat")
         data["pts_feat"] = feat
@@ -331,6 +344,23 @@ class PoseNet:
         eps = arch.SAMPLING_EPS
         steps = self.cfg.sampling_steps
         gb = self.global_batch
+        if self.cfg.ode_coupling == "object":
+            # one RK45 solve per object (gp_ode_sample_object): initial step, controller, dense output and denoise
+            # in the one call. A window's rows are its rows of the whole batch's prior draw, as the PC branch's
+            rows_total, row_off = R, 0
+            if self.object_window is not None:
+                total, first = (int(v) for v in self.object_window)
+                if not 0 <= first <= total - bs:
+                    raise ValueError(f"object_window: objects [{first}, {first + bs}) outside a batch of {total}")
+                rows_total, row_off = total * K, first * K
+            x0 = self._draw_prior(rows_total)[row_off:row_off + R] * sde.prior_sigma(T0)
+            if rep_init is not None:
+                x0 = rep_init.to(torch.float32) + x0
+            pose, q, nfev, status = self.heads.ode_sample_object(pobj, x0, K, center, T0, eps, steps,
+                                                                 rows_total=rows_total)
+            self.last_nfev_objects, self.last_status_objects = nfev, status
+            self.last_nfev = int(nfev.max())
+            return pose.view(bs, K, -1), q.view(bs, K, -1), None
         if gb is None:
             x0 = self._draw_prior(R) * sde.prior_sigma(T0)
         else:   # this shard's rows of the whole batch's prior draw
@@ -447,6 +477,9 @@ class PoseNet:
             raise NotImplementedError("get_likelihood needs agent_type='score'")
         if self.global_batch is not None:
             raise NotImplementedError("get_likelihood has no global-batch mode")
+        if self.cfg.sampler_mode[0] == "ode" and self.cfg.ode_coupling == "object":
+            raise NotImplementedError("ode_coupling='object' is not built for get_likelihood (its solve stays "
+                                      "batch-coupled: one step controller over every pose of the call)")
         self.is_testing = True
         bs, K = pose_samples.shape[0], pose_samples.shape[1]
         R = bs * K

@@ -49,6 +49,10 @@ class GenPoseConfig:
     # reference's cond_pc_sampler as evaluation calls it) | object (each object's own candidates: a pose then
     # does not depend on which other objects share the call; DESIGN "Per-object coupling")
     pc_coupling: str = "batch"
+    # the same choice for the ODE sampler (read only when sampler_mode[0] == "ode"): what RK45's step controller
+    # takes its error norms over: batch (one solve_ivp on every row of the call, as the reference's evaluation
+    # calls cond_ode_sampler) | object (one solve per object: its own steps, accept / reject and nfev)
+    ode_coupling: str = "batch"
 
     def copy(self, **kw) -> "GenPoseConfig":
         return replace(self, **kw)
@@ -76,3 +80,5 @@ class GenPoseConfig:
             raise ValueError(f"noise {self.noise}")
         if self.pc_coupling not in ("batch", "object"):
             raise ValueError(f"pc_coupling {self.pc_coupling!r} (batch | object)")
+        if self.ode_coupling not in ("batch", "object"):
+            raise ValueError(f"ode_coupling {self.ode_coupling!r} (batch | object)")

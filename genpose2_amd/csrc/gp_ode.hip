@@ -80,7 +80,8 @@ __device__ __forceinline__ double ode_stage_in(const double* const* kin, const d
 }
 // scipy's error term of entry e: err = (K^T E) h / scale, scale = atol + max(|y|, |y_new|) rtol; kv = K_6[e], the
 // derivative this stage just formed
-__device__ __forceinline__ double ode_err_term(const OdeStageArgs& a, const double* const* kin, double kv, double h,
+template <typename Args>   // OdeStageArgs, or the per-object OdeObjArgs (e, atol, rtol)
+__device__ __forceinline__ double ode_err_term(const Args& a, const double* const* kin, double kv, double h,
                                                size_t e, double y0, double y1) {
 #pragma clang fp contract(off)
     double acc = kin[0][e] * a.e[0];
@@ -780,9 +781,10 @@ extern "C" int gp_ode_dense(const double* const* kslots, const double* P7x4, con
     return gp_check_launch("ode_dense_kernel");
 }
 
-extern "C" int gp_ode_denoise(const gp_head_weights* w, const float* pobj, float t32, float sigma, float g2,
-                              float step, const double* x, int rows, int k, const float* pts_center, double* pose,
-                              double* q, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+// nt_rows: the row count that picks the tile class (rows; the whole batch's rows for a per-object slice)
+static int ode_denoise_impl(const gp_head_weights* w, const float* pobj, float t32, float sigma, float g2, float step,
+                            const double* x, int rows, int k, int nt_rows, const float* pts_center, double* pose,
+                            double* q, void* workspace, size_t workspace_bytes, hipStream_t stream) {
     GP_REQUIRE(w && pobj && x && pts_center && pose && q && workspace && rows >= 1 && k >= 1,
                "ode_denoise: bad arguments");
     GP_REQUIRE(workspace_bytes >= gp_ode_workspace_size(rows), "ode_denoise: workspace too small");
@@ -802,12 +804,19 @@ extern "C" int gp_ode_denoise(const gp_head_weights* w, const float* pobj, float
     a.rows = rows;
     a.kper = k;
     // the stage kernels' trunk and tile (exact fp32 without the f16 planes)
-    const int nt = ode_nt(w, rows);
+    const int nt = ode_nt(w, nt_rows);
     const dim3 grid((rows + 16 * nt - 1) / (16 * nt)), blk(EVAL_WV * 64);
     head_dispatch(w->pe2_h ? X3P : 0, nt, [&](auto pl, auto ntc) {
         hipLaunchKernelGGL((ode_denoise_kernel<pl.value, ntc.value>), grid, blk, 0, stream, a);
     });
     return gp_check_launch("ode_denoise_kernel");
+}
+
+extern "C" int gp_ode_denoise(const gp_head_weights* w, const float* pobj, float t32, float sigma, float g2,
+                              float step, const double* x, int rows, int k, const float* pts_center, double* pose,
+                              double* q, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+    return ode_denoise_impl(w, pobj, t32, sigma, g2, step, x, rows, k, rows, pts_center, pose, q, workspace,
+                            workspace_bytes, stream);
 }
 
 // ============================================================================ device-controlled RK45
@@ -1334,4 +1343,683 @@ extern "C" int gp_ode_sample(const gp_head_weights* w, const float* pobj, const 
     const float g = sig * (float)dscale;
     const float step = (float)((1.0 - eps) / (steps > 0 ? steps : 1000));
     return gp_ode_denoise(w, pobj, te, sig, g * g, step, x, rows, k, pts_center, pose, q, rws, rws_b, stream);
+}
+
+// ============================================================================ per-object RK45 (gp_ode_sample_object)
+// cond_ode_sampler as the reference runs it when called once per object on that object's k candidates: every
+// object has its own solve_ivp -- its own initial step, step controller, stage times, accept / reject and RMS
+// norms over its k * 9 elements -- so its result does not depend on which other objects share the call.
+//
+// One OdeObjRec per object, double-buffered per attempt parity as OdeCtl is. ode_obj_control_kernel (one workgroup
+// per object and slice of the 768-row) decides the object's last attempt from its rows' error sums and prepares
+// the next one: h, t_new, the six stage scalars, and the six rows init[s][b] = pobj[b] + tproj(t32[b][s]) (one fp32
+// add, the sum the trunks form themselves from pobj and tproj). The stages hand the trunk init[s] as its pobj and a
+// row of -0.0f as its tproj: x + (-0.0f) is x for every x, so a row's bits are those of the whole-batch stage at
+// the same t32 and the trunks stay as they are. ode_obj_attempt_kernel runs the six stages of every object's
+// attempt in one launch with the tiling of the whole batch (rows_total): h, coef, sigma and active / inactive are
+// per row, from the row's object record; a workgroup without an active row returns at once. The K slots and the
+// two state buffers keep their places: the workgroup that owns an accepted object's rows copies y_new -> y and
+// K_6 -> K_0 (FSAL) in the next attempt's prologue, and only when that object runs again, so a finished object's
+// y (the last step's start), y_new (its end) and K_0..K_6 stay for the dense output and are never written again.
+struct OdeObjRec {
+    double t, h_abs;              // solver time; step size carried to the next step (scipy self.h_abs)
+    double t_old;                 // start of the last accepted step (dense output; its h is t - t_old)
+    double h, t_new, h_abs_loc;   // the prepared attempt (scipy _step_impl locals h, t_new, h_abs)
+    double coef[6];               // -(0.5 g(t_s)^2) of the attempt's 6 stage times
+    float t32[6], sig[6];         // float32(t_s), sigma(t32)
+    int status;                   // 0 running, 1 finished, -1 step size below spacing (scipy failure)
+    int active;                   // the prepared attempt runs
+    int rejected;                 // scipy step_rejected within the current step
+    int nfev, n_acc;              // RHS evaluations, accepted steps
+    int pend;                     // the last decided attempt was accepted and y_new / K_6 are not yet copied to
+                                  // y / K_0: the state is in y_new
+};
+static_assert(sizeof(OdeObjRec) == 168, "OdeObjRec: doubles, floats, ints without padding");
+
+struct OdeObjArgs {
+    gp_head_weights w;
+    const float* init;            // (6, nobj, 768) folded rows of the prepared attempt
+    const float* zrow;            // (768) of -0.0f
+    const OdeObjRec* rec;         // (nobj) records of the prepared attempt
+    double* y;                    // (R,9) state at the step's start
+    double* ynew;                 // (R,9) the attempt's end
+    double* k[ODE_NK];            // K_0..K_6, fixed slots
+    double* f1;                   // (R,9) the Euler probe's derivative (select_initial_step)
+    double* rowsq;                // (R) sum over a row's 9 entries of (err/scale)^2, in increasing entry order
+    double e[ODE_NK];
+    double rtol, atol;
+    int rows, kper, nobj;
+    int single;                   // 0: an attempt; 1: K_0 = f(t, y); 2: f1 = f(t, y + K_0 h) (both with slot 0's row)
+};
+
+// sum_{j<n} v(j) by one wave in an order that is a function of j and n alone: lane l adds j = l, l + 64, ... in
+// increasing j from 0, the 64 lane sums meet in an xor tree. Every lane returns the sum.
+template <typename F>
+__device__ __forceinline__ double ode_obj_wave_sum(int n, F v) {
+#pragma clang fp contract(off)
+    double t = 0.0;
+    for (int j = threadIdx.x & 63; j < n; j += 64) t += v(j);
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) t += __shfl_xor(t, off, 64);
+    return t;
+}
+
+// ode_stage_body with h, coef, sigma and active / inactive per row (rh, rcoef, rsig, ract: LDS, one per row of the
+// tile; rh and ract set before the caller's last barrier). slot: which of the attempt's six rows and scalars.
+template <int MODE, int PL, int NT>
+__device__ __forceinline__ void ode_obj_stage_body(const OdeObjArgs& a, const double* const* kin, const double* acoef,
+                                                   int nk, int slot, double* kout, HeadSmem<NT, EVAL_WV, PL>& sm,
+                                                   const int* obj, const int* ract, const double* rh, double* rcoef,
+                                                   float* rsig, double* y0s, double* y1s, const SplitScalars& hs) {
+    constexpr int ROWS = 16 * NT;
+    constexpr int NTH = EVAL_WV * 64;
+    const int tid = threadIdx.x;
+    const int r0 = blockIdx.x * ROWS;
+    stage_small_weights(a.w, sm);
+    for (int i = tid; i < ROWS * 16; i += NTH) {
+        const int c = i >> 4, j = i & 15;
+        const int r = r0 + c;
+        float xv = 0.f;
+        if (r < a.rows && j < 9 && ract[c]) {
+            const size_t e = (size_t)r * 9 + j;
+            const double yv = a.y[e];
+            const double yi = nk > 0 ? ode_stage_in(kin, acoef, nk, rh[c], e, yv) : yv;
+            xv = (float)yi;   // torch.tensor(x, dtype=torch.float32) (samplers.py:210)
+            if (MODE == 1) {
+                y0s[c * 9 + j] = yv;
+                y1s[c * 9 + j] = yi;
+                a.ynew[e] = yi;
+            }
+        }
+        sm.xin[i] = xv;
+    }
+    if (tid < ROWS) {
+        const OdeObjRec* rc = a.rec + obj[tid];
+        rcoef[tid] = rc->coef[slot];
+        rsig[tid] = rc->sig[slot];
+    }
+    run_head_trunk(a.w, a.init + (size_t)slot * a.nobj * 768, a.zrow, obj, sm, 0, hs);
+    for (int e9 = tid; e9 < ROWS * 9; e9 += NTH) {
+#pragma clang fp contract(off)
+        const int c = e9 / 9, o = e9 - c * 9;
+        const int r = r0 + c;
+        if (r < a.rows && ract[c]) {
+            const size_t e = (size_t)r * 9 + o;
+            const float s = fdiv(head_out(sm, c, o), fadd(rsig[c], 1e-7f));
+            const double kv = rcoef[c] * (double)s;
+            kout[e] = kv;
+            if (MODE == 1) {
+                const double er = ode_err_term(a, kin, kv, rh[c], e, y0s[e9], y1s[e9]);
+                y1s[e9] = er * er;   // its own entry: read above by this thread only
+            }
+        }
+    }
+    if (MODE == 1) {
+        __syncthreads();
+        if (tid < ROWS && r0 + tid < a.rows && ract[tid]) {
+#pragma clang fp contract(off)
+            double sq = y1s[tid * 9];
+            for (int o = 1; o < 9; ++o) sq += y1s[tid * 9 + o];
+            a.rowsq[r0 + tid] = sq;
+        }
+    }
+}
+
+template <int PL, int NT>
+__global__ __launch_bounds__(EVAL_WV * 64) void ode_obj_attempt_kernel(OdeObjArgs a, OdeTableau tb) {
+    constexpr int ROWS = 16 * NT;
+    constexpr int NTH = EVAL_WV * 64;
+    static_assert(ROWS + 42 + ODE_NK <= NTH, "one thread per row, tableau entry and K slot");
+    __shared__ HeadSmem<NT, EVAL_WV, PL> sm;
+    __shared__ int obj[ROWS], ract[ROWS], rpend[ROWS];
+    __shared__ double rh[ROWS], rcoef[ROWS];
+    __shared__ float rsig[ROWS];
+    __shared__ double y0s[ROWS * 9], y1s[ROWS * 9];
+    __shared__ double tab[42];
+    __shared__ const double* kin[ODE_NK];
+    const int tid = threadIdx.x;
+    const int r0 = blockIdx.x * ROWS;
+    int act = 0;
+    if (tid < ROWS) {
+        const int o = obj_of_row(r0 + tid, a.rows, a.kper);
+        const OdeObjRec* rc = a.rec + o;
+        act = (r0 + tid < a.rows) && rc->active != 0;
+        obj[tid] = o;
+        ract[tid] = act;
+        rpend[tid] = rc->pend;
+        rh[tid] = rc->h;
+    } else if (tid < ROWS + 36) {
+        tab[tid - ROWS] = a.single ? 1.0 : tb.A[tid - ROWS];
+    } else if (tid < ROWS + 42) {
+        tab[tid - ROWS] = tb.B[tid - ROWS - 36];
+    } else if (tid < ROWS + 42 + ODE_NK) {
+        kin[tid - ROWS - 42] = a.k[tid - ROWS - 42];
+    }
+    if (!__syncthreads_or(act)) return;   // none of this workgroup's objects runs
+    if (a.single) {
+        const SplitScalars hs = load_split_scalars<PL>(a.w);
+        if (a.single == 1)
+            ode_obj_stage_body<0, PL, NT>(a, kin, tab, 0, 0, a.k[0], sm, obj, ract, rh, rcoef, rsig, y0s, y1s, hs);
+        else   // y + (K_0 * 1.0) h
+            ode_obj_stage_body<0, PL, NT>(a, kin, tab, 1, 0, a.f1, sm, obj, ract, rh, rcoef, rsig, y0s, y1s, hs);
+        return;
+    }
+    // the accepted step of the objects that go on: y_new -> y, K_6 -> K_0 (these rows are this workgroup's in every
+    // attempt; the barrier orders the stores before the stages' loads)
+    for (int e9 = tid; e9 < ROWS * 9; e9 += NTH) {
+        const int c = e9 / 9;
+        if (ract[c] && rpend[c]) {
+            const size_t e = (size_t)r0 * 9 + e9;
+            a.y[e] = a.ynew[e];
+            a.k[0][e] = a.k[ODE_NK - 1][e];
+        }
+    }
+    for (int s = 1; s < 6; ++s) {
+        __syncthreads();   // the copies above; stage s-1's K stores and its reads of the staged weights are done
+        const SplitScalars hs = load_split_scalars<PL>(a.w);
+        ode_obj_stage_body<0, PL, NT>(a, kin, tab + s * 6, s, s - 1, const_cast<double*>(kin[s]), sm, obj, ract, rh,
+                                      rcoef, rsig, y0s, y1s, hs);
+    }
+    __syncthreads();
+    const SplitScalars hs = load_split_scalars<PL>(a.w);
+    ode_obj_stage_body<1, PL, NT>(a, kin, tab + 36, 6, 5, const_cast<double*>(kin[6]), sm, obj, ract, rh, rcoef, rsig,
+                                  y0s, y1s, hs);
+}
+
+// dot_chains for P vectors x[p] (stride xs) against the same weight column: every weight is loaded once for the P
+// sums; each sum has dot_chains' own chains and tree, so its bits.
+template <int N, int CH, int P>
+__device__ __forceinline__ void dot_chains_multi(const float* __restrict__ W, size_t stride, const float* x, int xs,
+                                                 float (&out)[P]) {
+#if HOIST64
+    for (int q = 0; q < P; ++q) out[q] = (float)dot_f64<N>(W, stride, x + q * xs);
+#else
+    float p[P][CH];
+#pragma unroll
+    for (int q = 0; q < P; ++q)
+#pragma unroll
+        for (int j = 0; j < CH; ++j) p[q][j] = 0.f;
+#pragma unroll 1   // more loads in flight (unroll 4) measured no faster: the rows are bound by the weights' L2 stream
+    for (int c0 = 0; c0 < N; c0 += CH) {
+#pragma unroll
+        for (int j = 0; j < CH; ++j) {
+            const float wv = W[(size_t)(c0 + j) * stride];
+#pragma unroll
+            for (int q = 0; q < P; ++q) p[q][j] = fmaf(wv, x[q * xs + c0 + j], p[q][j]);
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < P; ++q) {
+#pragma unroll
+        for (int s = CH / 2; s >= 1; s >>= 1)
+#pragma unroll
+            for (int j = 0; j < s; ++j) p[q][j] += p[q][j + s];
+        out[q] = p[q][0];
+    }
+#endif
+}
+
+#define ODE_OBJ_CHUNKS 3   // workgroups per object (768 / 3 outputs each: one per thread and stage)
+
+// Decides attempt n-1 of object blockIdx.x (decide) and prepares its attempt n: ode_control_kernel's expressions
+// on the object's own error norm. ns time rows per object (6; 1 for the two select_initial_step evaluations, whose
+// records the host prepared: prepare = 0 then only forms init[0]). Every slice's workgroup of an object computes
+// the same record; slice 0 writes it and counts. count: one 64-bit word, objects arrived << 32 | objects running;
+// the last arriver writes 4 n + (running ? 1 : 2) to hstat[n & 3] (host-mapped, optional) and dstat[0], and zeroes
+// the word for the next attempt.
+__global__ __launch_bounds__(HT) void ode_obj_control_kernel(gp_head_weights w, const float* __restrict__ pobj,
+                                                             const OdeObjRec* __restrict__ cin,
+                                                             OdeObjRec* __restrict__ cout,
+                                                             const double* __restrict__ rowsq, int decide, int prepare,
+                                                             int ns, OdeConsts k, int kper, int nobj,
+                                                             float* __restrict__ init,
+                                                             unsigned long long* __restrict__ count,
+                                                             int* __restrict__ hstat, int* __restrict__ dstat, int n) {
+#pragma clang fp contract(off)
+    __shared__ OdeObjRec s;
+    __shared__ float emb[6 * 128], tf[6 * 128];
+    const int tid = threadIdx.x;
+    const int b = blockIdx.x;
+    const bool writer = tid == 0 && blockIdx.y == 0;
+    if (prepare) {
+        const bool run = decide && cin[b].active;
+        double esum = 0.0;
+        if (run && tid < 64) {   // the object's error sum over its rows, by wave 0
+            const double* rs = rowsq + (size_t)b * kper;
+            esum = ode_obj_wave_sum(kper, [&](int j) { return rs[j]; });
+        }
+        if (tid == 0) {
+            OdeObjRec c = cin[b];
+            const double dir = k.direction;
+            if (run) {   // scipy RK45._step_impl, after rk_step / _estimate_error_norm
+                const double err = sqrt(esum) / sqrt(k.count);
+                c.nfev += 6;
+                c.pend = 0;
+                if (err < 1.0) {
+                    double factor = err == 0.0 ? 10.0 : fmin(10.0, 0.9 * pow(err, -0.2));
+                    if (c.rejected) factor = fmin(1.0, factor);
+                    c.h_abs = c.h_abs_loc * factor;
+                    c.t_old = c.t;
+                    c.t = c.t_new;
+                    c.pend = 1;
+                    c.n_acc += 1;
+                    c.rejected = 0;
+                    if (dir * (c.t - k.t_bound) >= 0.0) c.status = 1;
+                } else {
+                    c.h_abs_loc *= fmax(0.2, 0.9 * pow(err, -0.2));
+                    c.rejected = 1;
+                }
+            }
+            c.active = 0;
+            if (c.status == 0) {   // prepare the next attempt
+                const double min_step = 10.0 * fabs(nextafter(c.t, dir * INFINITY) - c.t);
+                double ha = c.rejected ? c.h_abs_loc : (c.h_abs < min_step ? min_step : c.h_abs);
+                if (ha < min_step) {
+                    c.status = -1;
+                } else {
+                    double h = ha * dir;
+                    double t_new = c.t + h;
+                    if (dir * (t_new - k.t_bound) > 0.0) t_new = k.t_bound;
+                    h = t_new - c.t;
+                    c.h = h;
+                    c.t_new = t_new;
+                    c.h_abs_loc = fabs(h);
+                    c.active = 1;
+                }
+            }
+            s = c;
+        }
+        __syncthreads();
+        // stage times t + c_s h (s = 1..5) and t + h, one thread each (rk.py rk_step)
+        if (s.active && tid < 6) {
+            const double cs[5] = {1.0 / 5.0, 3.0 / 10.0, 4.0 / 5.0, 8.0 / 9.0, 1.0};
+            const double ts = tid < 5 ? s.t + cs[tid] * s.h : s.t + s.h;
+            const float t32 = (float)ts;
+            s.t32[tid] = t32;
+            s.sig[tid] = fmul((float)k.sig_min, (float)pow(k.base, (double)t32));
+            const double g = (k.sig_min * pow(k.base, ts)) * k.diff_scale;
+            s.coef[tid] = -(0.5 * (g * g));
+        }
+        __syncthreads();
+        if (writer) {
+            cout[b] = s;
+            const unsigned long long mine = (1ull << 32) | (s.active ? 1ull : 0ull);
+            const unsigned long long seen =
+                __hip_atomic_fetch_add(count, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + mine;
+            if ((int)(seen >> 32) == nobj) {   // the last object: every count is in `seen`
+                __hip_atomic_store(count, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                const int word = 4 * n + ((seen & 0xffffffffull) != 0 ? 1 : 2);
+                dstat[0] = word;
+                if (hstat != nullptr) {
+                    __threadfence_system();
+                    reinterpret_cast<volatile int*>(hstat)[n & 3] = word;
+                }
+            }
+        }
+    } else {
+        if (tid == 0) s = cin[b];
+        __syncthreads();
+    }
+    if (!s.active) return;
+    // the ns time rows of this object, the weights read once for all of them (time_row's sums per row)
+    if (tid < 64) {   // x_proj = x[:, None] * W[None, :] * 2 * np.pi (scorenet.py:87)
+        for (int q = 0; q < ns; ++q) {
+            const float av = fmul(fmul(fmul(s.t32[q], w.gfp_w[tid]), 2.0f), 3.14159265358979323846f);
+            emb[q * 128 + tid] = sinf(av);
+            emb[q * 128 + 64 + tid] = cosf(av);
+        }
+    }
+    for (int i = ns * 128 + tid; i < 6 * 128; i += HT) emb[i] = 0.f;   // unused rows: defined
+    __syncthreads();
+    if (tid < 128) {
+        float d[6];
+        dot_chains_multi<128, 16, 6>(w.te_w_t + tid, 128, emb, 128, d);
+#pragma unroll
+        for (int q = 0; q < 6; ++q) tf[q * 128 + tid] = fmaxf(d[q] + w.te_b[tid], 0.f);
+    }
+    __syncthreads();
+    constexpr int PER = 768 / ODE_OBJ_CHUNKS;
+    for (int o = blockIdx.y * PER + tid; o < blockIdx.y * PER + PER; o += HT) {
+        float d[6];
+        dot_chains_multi<128, 16, 6>(w.h1t_t + o, 768, tf, 128, d);
+        const float po = pobj[(size_t)b * 768 + o];
+#pragma unroll
+        for (int q = 0; q < 6; ++q)
+            if (q < ns) init[((size_t)q * nobj + b) * 768 + o] = fadd(po, d[q]);   // the trunks' pov + tpv
+    }
+}
+
+// select_initial_step norms of every object (scipy _ivp/common.py), one wave per object: scale = atol + |y0| rtol;
+// f1 == NULL: out[3 b] = rms(y0 / scale), out[3 b + 1] = rms(f0 / scale); else out[3 b + 2] = rms((f1 - f0) / scale),
+// each over the object's k * 9 elements: a row's 9 squares in entry order, the rows by ode_obj_wave_sum.
+__global__ __launch_bounds__(64) void ode_obj_init_norms_kernel(const double* __restrict__ y0,
+                                                                const double* __restrict__ f0,
+                                                                const double* __restrict__ f1, int kper, double atol,
+                                                                double rtol, double* __restrict__ out) {
+#pragma clang fp contract(off)
+    const int b = blockIdx.x;
+    const size_t base = (size_t)b * kper * 9;
+    auto row = [&](int j, int which) {
+        double sq = 0.0;
+        for (int o = 0; o < 9; ++o) {
+            const size_t e = base + (size_t)j * 9 + o;
+            const double sc = atol + fabs(y0[e]) * rtol;
+            const double v = which == 0 ? y0[e] / sc : (which == 1 ? f0[e] / sc : (f1[e] - f0[e]) / sc);
+            sq = o == 0 ? v * v : sq + v * v;
+        }
+        return sq;
+    };
+    const double rn = sqrt((double)kper * 9.0);
+    if (f1 == nullptr) {
+        const double s0 = ode_obj_wave_sum(kper, [&](int j) { return row(j, 0); });
+        const double s1 = ode_obj_wave_sum(kper, [&](int j) { return row(j, 1); });
+        if (threadIdx.x == 0) {
+            out[3 * b] = sqrt(s0) / rn;
+            out[3 * b + 1] = sqrt(s1) / rn;
+        }
+    } else {
+        const double s2 = ode_obj_wave_sum(kper, [&](int j) { return row(j, 2); });
+        if (threadIdx.x == 0) out[3 * b + 2] = sqrt(s2) / rn;
+    }
+}
+
+// res.y[:, -1] of every object: with t_eval set and the solve finished, the dense output of the object's last
+// accepted step at te (ode_dense_kernel's expressions with the object's t_old and h = t - t_old; its K_0..K_6 and
+// y, the step's start, are in place); else its state (y_new while the accepted step is not copied, else y).
+struct OdeObjFinalArgs {
+    const OdeObjRec* rec;
+    const double* y;
+    const double* ynew;
+    const double* k[ODE_NK];
+    double P[ODE_NK][4];
+    double te;
+    int dense, kper;
+    long long n;
+    double* out;
+};
+__global__ __launch_bounds__(256) void ode_obj_final_kernel(OdeObjFinalArgs a) {
+#pragma clang fp contract(off)
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= a.n) return;
+    const OdeObjRec* rc = a.rec + (e / 9) / a.kper;
+    if (!(a.dense && rc->status > 0)) {
+        a.out[e] = rc->pend ? a.ynew[e] : a.y[e];
+        return;
+    }
+    double Q[4];
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+        double acc = a.k[0][e] * a.P[0][m];
+        for (int j = 1; j < ODE_NK; ++j) acc = acc + a.k[j][e] * a.P[j][m];
+        Q[m] = acc;
+    }
+    const double h = rc->t - rc->t_old;
+    const double x = (a.te - rc->t_old) / h;
+    const double p1 = x, p2 = p1 * x, p3 = p2 * x, p4 = p3 * x;
+    const double d = ((Q[0] * p1 + Q[1] * p2) + Q[2] * p3) + Q[3] * p4;
+    a.out[e] = h * d + a.y[e];
+}
+
+__global__ void ode_obj_fill_kernel(float* __restrict__ p, int n, float v) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) p[i] = v;
+}
+
+namespace {
+struct OdeObjLayout {
+    size_t y, ynew, k[ODE_NK], f1, xout, rowsq, norms, rec, init, zrow, count, dstat, den_ws, total;
+};
+OdeObjLayout ode_obj_layout(int rows, int nobj) {
+    OdeObjLayout L = {};
+    const size_t vec = align256((size_t)rows * 9 * sizeof(double));
+    size_t off = 0;
+    L.y = off; off += vec;
+    L.ynew = off; off += vec;
+    for (int j = 0; j < ODE_NK; ++j) { L.k[j] = off; off += vec; }
+    L.f1 = off; off += vec;
+    L.xout = off; off += vec;
+    L.rowsq = off; off += align256((size_t)rows * sizeof(double));
+    L.norms = off; off += align256((size_t)nobj * 3 * sizeof(double));
+    L.rec = off; off += align256((size_t)nobj * 2 * sizeof(OdeObjRec));
+    L.init = off; off += align256((size_t)nobj * 6 * 768 * sizeof(float));
+    L.zrow = off; off += align256(768 * sizeof(float));
+    L.count = off; off += 256;
+    L.dstat = off; off += 256;
+    L.den_ws = off; off += align256(gp_ode_workspace_size(rows));
+    L.total = off;
+    return L;
+}
+}  // namespace
+
+extern "C" size_t gp_ode_object_workspace_size_k(int rows, int k) {
+    return (rows >= 1 && k >= 1 && rows % k == 0) ? ode_obj_layout(rows, rows / k).total : 0;
+}
+// enough for every k (k = 1: one record and six rows per candidate)
+extern "C" size_t gp_ode_object_workspace_size(int rows) { return gp_ode_object_workspace_size_k(rows, 1); }
+
+extern "C" int gp_ode_sample_object(const gp_head_weights* w, const float* pobj, const float* x0, int rows, int k,
+                                    int rows_total, double T0, double eps, int steps, double rtol, double atol,
+                                    const float* pts_center, double* pose, double* q, int* nfev_out, int* status_out,
+                                    void* workspace, size_t workspace_bytes, hipStream_t stream) {
+    GP_REQUIRE(w && pobj && x0 && pts_center && pose && q && workspace && rows >= 1 && k >= 1 && steps >= 0,
+               "ode_sample_object: bad arguments");
+    GP_REQUIRE(rows % k == 0, "ode_sample_object: rows %d are not whole objects of k = %d", rows, k);
+    GP_REQUIRE(rows_total >= rows && rows_total % k == 0,
+               "ode_sample_object: rows_total %d must be whole objects and hold this call's %d rows", rows_total, rows);
+    GP_REQUIRE(T0 != eps, "ode_sample_object: empty integration interval (T0 == eps)");
+    GP_REQUIRE(steps != 1, "ode_sample_object: steps must be 0 (t_eval unset) or >= 2");
+    const int nobj = rows / k;
+    const OdeObjLayout L = ode_obj_layout(rows, nobj);
+    GP_REQUIRE(workspace_bytes >= L.total,
+               "ode_sample_object: workspace too small (gp_ode_object_workspace_size_k(rows, k))");
+    StatusLease status;
+    GP_REQUIRE(status.acquire(stream) == 0, "ode_sample_object: pinned status word / event");
+    char* ws = static_cast<char*>(workspace);
+    auto dptr = [&](size_t off) { return reinterpret_cast<double*>(ws + off); };
+    OdeObjRec* rec = reinterpret_cast<OdeObjRec*>(ws + L.rec);   // rec[parity * nobj + b]
+    float* init = reinterpret_cast<float*>(ws + L.init);
+    float* zrow = reinterpret_cast<float*>(ws + L.zrow);
+    unsigned long long* count = reinterpret_cast<unsigned long long*>(ws + L.count);
+    int* dstat = reinterpret_cast<int*>(ws + L.dstat);
+    double* norms = dptr(L.norms);
+    const long long n = (long long)rows * 9;
+    const double t0 = T0, tf = eps, dir = tf > t0 ? 1.0 : -1.0;
+    const double dscale = diff_scale();
+    const int nt = ode_nt(w, rows_total);   // the whole batch's tile class
+    const int nwg = (rows + 16 * nt - 1) / (16 * nt);
+    const OdeConsts kc = {tf, dir, rtol, atol, kSigMin, kBase, dscale, (double)k * 9.0, 0};
+
+    OdeObjArgs a = {};
+    a.w = *w;
+    a.init = init;
+    a.zrow = zrow;
+    a.y = dptr(L.y);
+    a.ynew = dptr(L.ynew);
+    for (int j = 0; j < ODE_NK; ++j) {
+        a.k[j] = dptr(L.k[j]);
+        a.e[j] = kE7[j];
+    }
+    a.f1 = dptr(L.f1);
+    a.rowsq = dptr(L.rowsq);
+    a.rtol = rtol;
+    a.atol = atol;
+    a.rows = rows;
+    a.kper = k;
+    a.nobj = nobj;
+    OdeTableau tb;
+    for (int j = 0; j < 36; ++j) tb.A[j] = kA6[j];
+    for (int j = 0; j < 6; ++j) tb.B[j] = kB6[j];
+    auto stages = [&](const OdeObjRec* r, int single) {
+        a.rec = r;
+        a.single = single;
+        const dim3 grid(nwg), blk(EVAL_WV * 64);
+        head_dispatch(w->pe2_h ? X3P : 0, nt, [&](auto pl, auto ntc) {
+            hipLaunchKernelGGL((ode_obj_attempt_kernel<pl.value, ntc.value>), grid, blk, 0, stream, a, tb);
+        });
+        return gp_check_launch("ode_obj_attempt_kernel");
+    };
+    // rows of slot 0 for host-prepared records (the two select_initial_step evaluations)
+    auto rows0 = [&](const OdeObjRec* r) {
+        hipLaunchKernelGGL(ode_obj_control_kernel, dim3(nobj, ODE_OBJ_CHUNKS), dim3(HT), 0, stream, *w, pobj, r,
+                           (OdeObjRec*)nullptr, (const double*)nullptr, 0, 0, 1, kc, k, nobj, init, count,
+                           (int*)nullptr, dstat, 0);
+        return gp_check_launch("ode_obj_control_kernel<rows>");
+    };
+    int rc;
+    GP_REQUIRE(hipMemsetAsync(count, 0, 256, stream) == hipSuccess, "ode_sample_object: counter");
+    hipLaunchKernelGGL(ode_obj_fill_kernel, dim3(3), dim3(256), 0, stream, zrow, 768, -0.0f);
+    hipLaunchKernelGGL(f32_to_f64_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, x0, a.y, n);
+    if ((rc = gp_check_launch("f32_to_f64_kernel"))) return rc;
+
+    // ---- select_initial_step (scipy common.py) per object, gp_ode_sample's scalar expressions element by element
+    std::vector<OdeObjRec> hrec((size_t)nobj);
+    std::vector<double> hn((size_t)nobj * 3);
+    auto upload = [&](int parity) {
+        return hipMemcpyAsync(rec + (size_t)parity * nobj, hrec.data(), sizeof(OdeObjRec) * (size_t)nobj,
+                              hipMemcpyHostToDevice, stream) == hipSuccess &&
+               hipStreamSynchronize(stream) == hipSuccess;
+    };
+    auto norms_back = [&]() {
+        return hipMemcpyAsync(hn.data(), norms, sizeof(double) * 3 * (size_t)nobj, hipMemcpyDeviceToHost, stream) ==
+                   hipSuccess && hipStreamSynchronize(stream) == hipSuccess;
+    };
+    {   // f(t0): solve_ivp hands t0 as a Python float, so ode_func's g is float32 sigma * float64 scale
+        const float t32 = (float)t0;
+        const double g = (double)sigma32(t32) * dscale;
+        for (int b = 0; b < nobj; ++b) {
+            OdeObjRec r = {};
+            r.t = t0;
+            r.active = 1;
+            r.t32[0] = t32;
+            r.sig[0] = sigma32(t32);
+            r.coef[0] = -(0.5 * (g * g));
+            hrec[(size_t)b] = r;
+        }
+    }
+    GP_REQUIRE(upload(0), "ode_sample_object: records");
+    if ((rc = rows0(rec))) return rc;
+    if ((rc = stages(rec, 1))) return rc;
+    hipLaunchKernelGGL(ode_obj_init_norms_kernel, dim3(nobj), dim3(64), 0, stream, (const double*)a.y,
+                       (const double*)a.k[0], (const double*)nullptr, k, atol, rtol, norms);
+    if ((rc = gp_check_launch("ode_obj_init_norms_kernel"))) return rc;
+    GP_REQUIRE(norms_back(), "ode_sample_object: norm read");
+    const double interval = fabs(tf - t0);
+    std::vector<double> h0v((size_t)nobj);
+    for (int b = 0; b < nobj; ++b) {
+        const double d0 = hn[3 * (size_t)b], d1 = hn[3 * (size_t)b + 1];
+        double h0 = (d0 < 1e-5 || d1 < 1e-5) ? 1e-6 : 0.01 * d0 / d1;
+        h0 = fmin(h0, interval);
+        h0v[(size_t)b] = h0;
+        // f(t0 + h0 dir, y0 + h0 dir f0): a NumPy float64 time from here on
+        const double t = t0 + h0 * dir;
+        const double g = kSigMin * pow(kBase, t) * dscale;
+        OdeObjRec& r = hrec[(size_t)b];
+        r.h = h0 * dir;
+        r.t32[0] = (float)t;
+        r.sig[0] = sigma32((float)t);
+        r.coef[0] = -(0.5 * (g * g));
+    }
+    GP_REQUIRE(upload(1), "ode_sample_object: records");
+    if ((rc = rows0(rec + nobj))) return rc;
+    if ((rc = stages(rec + nobj, 2))) return rc;
+    hipLaunchKernelGGL(ode_obj_init_norms_kernel, dim3(nobj), dim3(64), 0, stream, (const double*)a.y,
+                       (const double*)a.k[0], (const double*)a.f1, k, atol, rtol, norms);
+    if ((rc = gp_check_launch("ode_obj_init_norms_kernel"))) return rc;
+    GP_REQUIRE(norms_back(), "ode_sample_object: norm read");
+    for (int b = 0; b < nobj; ++b) {
+        const double d1 = hn[3 * (size_t)b + 1], h0 = h0v[(size_t)b];
+        const double d2 = hn[3 * (size_t)b + 2] / h0;
+        const double h1 = (d1 <= 1e-15 && d2 <= 1e-15) ? fmax(1e-6, h0 * 1e-3) : pow(0.01 / fmax(d1, d2), 1.0 / 5.0);
+        OdeObjRec r = {};
+        r.t = t0;
+        r.h_abs = fmin(fmin(100 * h0, h1), interval);
+        r.nfev = 2;
+        hrec[(size_t)b] = r;
+    }
+    GP_REQUIRE(upload(0), "ode_sample_object: records");
+
+    // ---- the attempts, one enqueued ahead of the status read; the loop ends when no object runs
+    int* hs_dev = nullptr;   // the pinned words as the device addresses them, if it can
+    {
+        const char* zc = getenv("GENPOSE2_ODE_ZC");
+        if ((zc != nullptr && zc[0] == '0') ||
+            hipHostGetDevicePointer(reinterpret_cast<void**>(&hs_dev), status.r.pinned, 0) != hipSuccess) {
+            hs_dev = nullptr;
+            (void)hipGetLastError();
+        }
+    }
+    auto control = [&](int at) {   // decides attempt at - 1, prepares attempt at
+        hipLaunchKernelGGL(ode_obj_control_kernel, dim3(nobj, ODE_OBJ_CHUNKS), dim3(HT), 0, stream, *w, pobj,
+                           (const OdeObjRec*)(rec + (size_t)(at & 1) * nobj), rec + (size_t)((at + 1) & 1) * nobj,
+                           (const double*)a.rowsq, at > 0 ? 1 : 0, 1, 6, kc, k, nobj, init, count, hs_dev, dstat, at);
+        return gp_check_launch("ode_obj_control_kernel");
+    };
+    auto attempt = [&](int at) { return stages(rec + (size_t)((at + 1) & 1) * nobj, 0); };
+    int at = 0;
+    if (hs_dev != nullptr) {
+        volatile int* hv = status.r.pinned;
+        for (int i = 0; i < 4; ++i) hv[i] = -1;
+        status.pending = true;   // the device writes the words until the stream drains
+        if ((rc = control(0)) || (rc = attempt(0))) return rc;
+        for (;; ++at) {
+            GP_REQUIRE(at < 100000, "ode_sample_object: attempt limit reached");
+            if ((rc = control(at + 1)) || (rc = attempt(at + 1))) return rc;
+            const int want = at + 1;
+            const auto t_end = std::chrono::steady_clock::now() + std::chrono::seconds(60);
+            int v;
+            while (((v = hv[want & 3]) >> 2) != want)
+                GP_REQUIRE(std::chrono::steady_clock::now() < t_end, "ode_sample_object: no status from attempt %d",
+                           want);
+            if ((v & 3) != 1) break;
+        }
+    } else {
+        if ((rc = control(0)) || (rc = attempt(0))) return rc;
+        for (;; ++at) {
+            GP_REQUIRE(at < 100000, "ode_sample_object: attempt limit reached");
+            if ((rc = control(at + 1))) return rc;
+            status.pending = true;
+            GP_REQUIRE(hipMemcpyAsync(status.r.pinned, dstat, 4, hipMemcpyDeviceToHost, stream) == hipSuccess &&
+                           hipEventRecord(status.r.ev, stream) == hipSuccess, "ode_sample_object: status read");
+            if ((rc = attempt(at + 1))) return rc;   // a no-op once no object runs
+            GP_REQUIRE(hipEventSynchronize(status.r.ev) == hipSuccess, "ode_sample_object: status wait");
+            status.pending = false;
+            GP_REQUIRE((*status.r.pinned >> 2) == at + 1, "ode_sample_object: status word of attempt %d", at + 1);
+            if ((*status.r.pinned & 3) != 1) break;
+        }
+    }
+    const OdeObjRec* fin = rec + (size_t)((at + 2) & 1) * nobj;
+    GP_REQUIRE(hipMemcpyAsync(hrec.data(), fin, sizeof(OdeObjRec) * (size_t)nobj, hipMemcpyDeviceToHost, stream) ==
+                       hipSuccess && hipStreamSynchronize(stream) == hipSuccess, "ode_sample_object: final records");
+    status.pending = false;
+    bool failed = false;
+    for (int b = 0; b < nobj; ++b) {
+        if (status_out) status_out[b] = hrec[(size_t)b].status;
+        if (nfev_out) nfev_out[b] = hrec[(size_t)b].nfev;
+        failed = failed || hrec[(size_t)b].status < 0;
+    }
+    GP_REQUIRE(!(failed && steps > 0),
+               "ode_sample_object: RK45 failed (step size below the spacing of t) with t_eval set: the collected "
+               "t_eval outputs need the host controller (genpose2_amd/ode.py rk45_drive)");
+    OdeObjFinalArgs fa = {};
+    fa.rec = fin;
+    fa.y = a.y;
+    fa.ynew = a.ynew;
+    for (int j = 0; j < ODE_NK; ++j) {
+        fa.k[j] = a.k[j];
+        for (int m = 0; m < 4; ++m) fa.P[j][m] = kP74[j * 4 + m];
+    }
+    fa.te = eps;
+    fa.dense = steps > 0;
+    fa.kper = k;
+    fa.n = n;
+    fa.out = dptr(L.xout);
+    hipLaunchKernelGGL(ode_obj_final_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, fa);
+    if ((rc = gp_check_launch("ode_obj_final_kernel"))) return rc;
+    // ---- denoise (samplers.py:240-249) with eps's scalars: a float32 1-element tensor for g
+    const float te = (float)eps;
+    const float sig = sigma32(te);
+    const float g = sig * (float)dscale;
+    const float step = (float)((1.0 - eps) / (steps > 0 ? steps : 1000));
+    return ode_denoise_impl(w, pobj, te, sig, g * g, step, fa.out, rows, k, rows_total, pts_center, pose, q,
+                            ws + L.den_ws, gp_ode_workspace_size(rows), stream);
 }

@@ -224,6 +224,7 @@ class HeadModel:
             raise ValueError(f"GENPOSE2_PC_SMALL={self.pc_small!r} (f16 | fp8 | auto)")
         self.set_arith(os.environ.get("GENPOSE2_HEAD_ARITH", "f16x3"))
         self._pc_ws: Optional[torch.Tensor] = None
+        self._ode_obj_ws: Optional[torch.Tensor] = None
         self._gw = None                                    # (buffers, HeadGradWeights)
 
     def weights_changed(self) -> None:
@@ -437,6 +438,31 @@ class HeadModel:
             ctypes.c_void_p(self._pc_ws.data_ptr()), self._pc_ws.numel(), self._s()), "pc_sample_object")
         return res, q, xs
 
+    def ode_sample_object(self, pobj, x0: torch.Tensor, k: int, pts_center: torch.Tensor, T0: float, eps: float,
+                          steps: Optional[int], rows_total=None, rtol: float = 1e-5, atol: float = 1e-5):
+        """cond_ode_sampler with one RK45 solve per object (gp_ode_sample_object): x0 (R,9) fp32, the prior sample
+        [+ init_x] at T0 -> pose (R,9), q (R,7) fp64, and per object nfev and status (NumPy int32, R // k). The
+        call's rows may be a slice of a batch of ``rows_total`` rows (default R), which picks the tile class."""
+        R = x0.shape[0]
+        rows_total = R if rows_total is None else int(rows_total)
+        x0 = x0.to(self.device, torch.float32).contiguous()
+        need = int(self.lib.gp_ode_object_workspace_size_k(R, k)) if k >= 1 and R % k == 0 else 0
+        if self._ode_obj_ws is None or self._ode_obj_ws.numel() < need:
+            self._ode_obj_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        pose = torch.empty((R, arch.POSE_DIM), dtype=torch.float64, device=self.device)
+        q = torch.empty((R, 7), dtype=torch.float64, device=self.device)
+        nobj = max(R // max(k, 1), 1)
+        nfev = np.zeros(nobj, np.int32)
+        status = np.zeros(nobj, np.int32)
+        pi = ctypes.POINTER(ctypes.c_int)
+        check(self.lib.gp_ode_sample_object(
+            ctypes.byref(self.w), ctypes.c_void_p(pobj.data_ptr()), ctypes.c_void_p(x0.data_ptr()), R, k, rows_total,
+            float(T0), float(eps), 0 if steps is None else int(steps), float(rtol), float(atol),
+            ctypes.c_void_p(require_device_tensor(pts_center, "pts_center").data_ptr()),
+            ctypes.c_void_p(pose.data_ptr()), ctypes.c_void_p(q.data_ptr()), nfev.ctypes.data_as(pi),
+            status.ctypes.data_as(pi), ctypes.c_void_p(self._ode_obj_ws.data_ptr()), self._ode_obj_ws.numel(),
+            self._s()), "ode_sample_object")
+        return pose, q, nfev, status
 
     def ode_denoise(self, pobj, t32: float, sigma: float, g2: float, step: float, x: torch.Tensor, k: int,
                     pts_center: torch.Tensor, ws: torch.Tensor):

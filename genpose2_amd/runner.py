@@ -129,6 +129,13 @@ class EvaluationPipeline:
 
 # ============================================================================ process_batch
 
+def object_coupled(cfg: GenPoseConfig) -> Optional[str]:
+    """The config field that couples the sampler in use per object ("pc_coupling" / "ode_coupling"), or None: a
+    shard of such a sampler runs as an ``object_window`` of the whole batch and needs no collective."""
+    field = {"pc": "pc_coupling", "ode": "ode_coupling"}.get(cfg.sampler_mode[0])
+    return field if field is not None and getattr(cfg, field) == "object" else None
+
+
 class ShardedEvaluationPipeline:
     """EvaluationPipeline over one process group (config 4: B=2048 objects over 8 GPUs).
 
@@ -146,7 +153,9 @@ class ShardedEvaluationPipeline:
     ``cfg.pc_coupling == "object"`` needs none of that: every rank's score agent gets its shard as
     ``object_window``, so its rows run the whole batch's tile class, prior rows and device draws, and each object's
     poses are bit for bit those of one call on the whole batch, with no collective on the sampling path
-    (``global_batch=True`` is refused with it)."""
+    (``global_batch=True`` is refused with it). ``cfg.ode_coupling == "object"`` does the same for the ODE sampler:
+    one RK45 solve per object, so a shard's poses and nfev are those of the one call, without the per-attempt
+    exchange."""
 
     def __init__(self, cfg: GenPoseConfig, with_energy: bool = True, with_scale: bool = False, src: int = 0,
                  global_batch: bool = False):
@@ -156,6 +165,9 @@ class ShardedEvaluationPipeline:
         if global_batch and self.local.cfg.pc_coupling == "object":
             raise NotImplementedError("pc_coupling='object' needs no global batch: a shard's objects do not depend "
                                       "on the other shards'")
+        if global_batch and object_coupled(self.local.cfg) == "ode_coupling":
+            raise NotImplementedError("ode_coupling='object' needs no global batch: a shard's objects have their own "
+                                      "RK45 solves")
         self.sync_weights()
 
     def agents(self):
@@ -195,7 +207,7 @@ class ShardedEvaluationPipeline:
         if self.global_batch:
             self.local.score_agent.global_batch = shard.GlobalBatch.of(total)   # raises on an empty shard
         if hi > lo:
-            if self.local.cfg.pc_coupling == "object":
+            if self.local.cfg.pc_coupling == "object" or object_coupled(self.local.cfg) is not None:
                 self.local.score_agent.object_window = (total, lo)
             # per-object tensors, and lists of them (the DINOv3 layers of --dino pointwise)
             try:

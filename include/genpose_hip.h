@@ -494,6 +494,31 @@ int gp_ode_sample(const gp_head_weights *w, const float *pobj, const float *x0, 
                   double T0, double eps, int steps, double rtol, double atol,
                   const float *pts_center, double *pose, double *q, int *nfev, int *status,
                   void *workspace, size_t workspace_bytes, hipStream_t stream);
+/* Per-object ODE sampling: cond_ode_sampler as the reference runs it when called once per object on that
+ * object's k candidates. Every object has its own solve_ivp(RK45): its own select_initial_step, step controller,
+ * stage times, accept / reject and RMS norms over its k * 9 elements (gp_ode_sample takes them over every row of
+ * the call). A norm's sum is taken per row over its 9 entries in increasing order, then over the object's rows
+ * j < k in an order that is a function of j and k alone (lane j % 64 of a wave adds its rows in increasing j, the
+ * lanes meet in an xor tree). rows (whole objects: a multiple of k) are a slice of a batch of rows_total rows
+ * (whole objects, >= rows): rows_total selects the tile class (gp_pc_tile_rows(rows_total, split)). pobj, x0,
+ * pts_center and the outputs hold this call's objects and rows only.
+ * HOST outs, one per object (rows / k; either may be NULL): nfev (2 + 6 attempts), status (1 done, -1 step size
+ * below the spacing of t; with steps > 0 any failed object returns an error, as gp_ode_sample does). A finished or
+ * failed object is not written again while the others go on; the call runs as many attempts as its slowest object.
+ * Contract: an object's pose, q, nfev, accepted steps and status are bit-identical for any set of other objects in
+ * the call and for any split of a batch into calls, given the same rows_total, x0 rows, weights and arithmetic,
+ * T0, eps, steps, rtol and atol. No exchange between ranks.
+ * Workspace: gp_ode_object_workspace_size_k(rows, k) bytes (six 768-rows per object and attempt);
+ * gp_ode_object_workspace_size(rows) is enough for every k. Status reads as gp_ode_sample: host-mapped words the
+ * device writes once per attempt (running or not, never one read per object), or an event and a 4-byte copy when
+ * the words cannot be mapped or GENPOSE2_ODE_ZC=0. Bad arguments return a status and set gp_last_error() before
+ * anything is launched. */
+size_t gp_ode_object_workspace_size(int rows);
+size_t gp_ode_object_workspace_size_k(int rows, int k);
+int gp_ode_sample_object(const gp_head_weights *w, const float *pobj, const float *x0, int rows, int k,
+                         int rows_total, double T0, double eps, int steps, double rtol, double atol,
+                         const float *pts_center, double *pose, double *q, int *nfev, int *status,
+                         void *workspace, size_t workspace_bytes, hipStream_t stream);
 /* Final denoise (samplers.py:240-249) + epilogue: grad = score(float(x), t32) fp32,
  * x + (0 - g2 * grad) * step (fp32 product, fp64 sum), GS of [:6], + pts_center, quaternion
  * (posenet_agent.py:554-556) -> pose (R,9) fp64, q (R,7) fp64. */
