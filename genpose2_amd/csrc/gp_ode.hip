@@ -2023,3 +2023,24 @@ extern "C" int gp_ode_sample_object(const gp_head_weights* w, const float* pobj,
     return ode_denoise_impl(w, pobj, te, sig, g * g, step, fa.out, rows, k, rows_total, pts_center, pose, q,
                             ws + L.den_ws, gp_ode_workspace_size(rows), stream);
 }
+
+// Test aid: one launch of ode_obj_control_kernel as gp_ode_sample_object launches it for an attempt (prepare = 1,
+// six time rows, the sampler's sigma constants), on caller-owned device buffers. rec_in / rec_out: nobj records of
+// gp_debug_ode_obj_rec_size() bytes each; rowsq (nobj * kper) the rows' error sums, read when decide != 0;
+// init (6, nobj, 768); count: one zeroed 64-bit word; host_status: NULL or 4 host-mapped ints as the device
+// addresses them; dev_status: one int. Not part of the sampler's ABI contract.
+extern "C" size_t gp_debug_ode_obj_rec_size(void) { return sizeof(OdeObjRec); }
+
+extern "C" int gp_debug_ode_obj_control(const gp_head_weights* w, const float* pobj, const void* rec_in, void* rec_out,
+                                        const double* rowsq, int decide, int n, double t_bound, double direction,
+                                        int kper, int nobj, float* init, unsigned long long* count, int* host_status,
+                                        int* dev_status, hipStream_t stream) {
+    GP_REQUIRE(w && pobj && rec_in && rec_out && init && count && dev_status && kper >= 1 && nobj >= 1 && n >= 0,
+               "debug_ode_obj_control: bad arguments");
+    GP_REQUIRE(!decide || rowsq, "debug_ode_obj_control: decide without row sums");
+    const OdeConsts kc = {t_bound, direction, 0.0, 0.0, kSigMin, kBase, diff_scale(), (double)kper * 9.0, 0};
+    hipLaunchKernelGGL(ode_obj_control_kernel, dim3(nobj, ODE_OBJ_CHUNKS), dim3(HT), 0, stream, *w, pobj,
+                       static_cast<const OdeObjRec*>(rec_in), static_cast<OdeObjRec*>(rec_out), rowsq,
+                       decide ? 1 : 0, 1, 6, kc, kper, nobj, init, count, host_status, dev_status, n);
+    return gp_check_launch("ode_obj_control_kernel<debug>");
+}

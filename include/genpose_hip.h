@@ -281,6 +281,21 @@ int gp_energy_score_eval(const gp_head_weights *w, const gp_head_grad_weights *g
 int gp_debug_q8_probe(const uint16_t *f16_bits, int n, int plane, uint8_t *q8, uint8_t *q8_via_f32,
                       hipStream_t stream);
 
+/* Test aid for the per-object RK45 controller (gp_ode_sample_object): one launch of its control kernel as the
+ * sampler launches it for attempt n, on caller-owned DEVICE buffers. It decides attempt n - 1 of every object from
+ * rowsq (nobj * kper: per row, the sum over its 9 entries of (err/scale)^2; read when decide != 0) and prepares
+ * attempt n. rec_in / rec_out: nobj controller records of gp_debug_ode_obj_rec_size() (168) bytes each, laid out as
+ * doubles t, h_abs, t_old, h, t_new, h_abs_loc, coef[6]; floats t32[6], sig[6]; ints status, active, rejected,
+ * nfev, n_acc, pend. init (6, nobj, 768): row [s][b] = pobj[b] + the time row of t32[b][s], written for the objects
+ * that run. count: one 64-bit word, zero on entry and on return. dev_status[0], and host_status[n & 3] when
+ * host_status (host-mapped memory as the device addresses it) is given, receive 4 n + 1 while any object runs and
+ * 4 n + 2 once none does. Not part of the sampler's contract: the sampler does not call it. */
+size_t gp_debug_ode_obj_rec_size(void);
+int gp_debug_ode_obj_control(const gp_head_weights *w, const float *pobj, const void *rec_in, void *rec_out,
+                             const double *rowsq, int decide, int n, double t_bound, double direction, int kper,
+                             int nobj, float *init, unsigned long long *count, int *host_status, int *dev_status,
+                             hipStream_t stream);
+
 /* ===================================================================== PC sampler
  * cond_pc_sampler (samplers.py:113-177) for R = b*k rows over T steps, fused per step:
  * [finish step i-1: Langevin corrector with the batch-mean score norm, renormalise,
