@@ -5,7 +5,8 @@ architecture, independent of genpose2_amd/dino.py's packing (no folding, no inte
 
 The ``variant`` switches exist only to prove that a fixture can see a mistake: "no_rope" (q, k not rotated),
 "swap_hw" (the h and w angle halves exchanged), "no_mask" (qkv.bias_mask ignored), "rope_prefix" (the 5 prefix
-tokens rotated too, with the first patches' angles).
+tokens rotated too, with the first patches' angles), "zero_key_tail" ((-n) % 16 all-zero key / value rows appended
+after RoPE and left unmasked in the softmax: an attention kernel that pads its last 16-key tile and loses the mask).
 """
 from __future__ import annotations
 
@@ -17,7 +18,7 @@ import torch
 import torch.nn.functional as F
 
 D, HEADS, HEAD_DIM, PATCH, PREFIX, BLOCKS, EPS = 384, 6, 64, 16, 5, 12, 1e-5
-VARIANTS = ("no_rope", "swap_hw", "no_mask", "rope_prefix")
+VARIANTS = ("no_rope", "swap_hw", "no_mask", "rope_prefix", "zero_key_tail")
 
 
 def rope_cos_sin(hp: int, wp: int, periods: Optional[torch.Tensor], dtype, device="cpu", swap_hw: bool = False
@@ -82,6 +83,9 @@ def forward(sd: Dict[str, np.ndarray], x, layers: Sequence[int] = (2, 6, 11), dt
             bias = bias * g(p + "attn.qkv.bias_mask")
         qkv = F.linear(y, g(p + "attn.qkv.weight"), bias).reshape(B, n, 3, HEADS, HEAD_DIM).permute(2, 0, 3, 1, 4)
         q, k, v = rot(qkv[0]), rot(qkv[1]), qkv[2]
+        if variant == "zero_key_tail" and (-n) % 16:
+            pad = k.new_zeros(k.shape[:2] + ((-n) % 16, HEAD_DIM))
+            k, v = torch.cat([k, pad], dim=2), torch.cat([v, pad], dim=2)
         att = torch.softmax(q @ k.transpose(-1, -2) * (HEAD_DIM ** -0.5), dim=-1) @ v       # (B, heads, n, 64)
         att = att.transpose(1, 2).reshape(B, n, D)
         h = h + g(p + "ls1.gamma") * F.linear(att, g(p + "attn.proj.weight"), g(p + "attn.proj.bias"))

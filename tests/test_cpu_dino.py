@@ -148,8 +148,10 @@ def test_fixture_c_layout():
     assert [r.shape for r in g["ref64"]] == [(1, 256, 384)] * 3 and g["ref64"][0].dtype == np.float64
     assert g["stats32"].shape == (3, 3) and np.all(g["stats32"] > 0) and np.all(g["stats32"][:, 0] < 1e-5)
     f = np.load(di.fixture_paths("c")[0])
-    for v in dino_ref.VARIANTS:       # every switched-off variant was visible when the fixture was made
-        assert float(f[f"ratio_{v}"]) >= 100.0
+    recorded = sorted(k[len("ratio_"):] for k in f.files if k.startswith("ratio_"))
+    assert recorded == ["no_mask", "no_rope", "rope_prefix", "swap_hw"]   # the variants dino_ref had at that time
+    for v in recorded:                # every switched-off variant was visible when the fixture was made
+        assert v in dino_ref.VARIANTS and float(f[f"ratio_{v}"]) >= 100.0
 
 
 def test_variants_move_the_output(dino_sd):

@@ -122,6 +122,145 @@ def test_linear_split_vs_torch(lib, m, k, n, act, pad):
         assert torch.all(y[:, n:] == 0)
 
 
+def _spread_rows(m, k, g):
+    """test_linear_split_vs_torch's input: per-row magnitudes spread by exp(3 randn), one all-zero row (m > 1)."""
+    x = torch.randn(m, k, generator=g) * torch.exp(torch.randn(m, 1, generator=g) * 3)
+    if m > 1:
+        x[m // 2] = 0.0
+    return x
+
+
+def _linear_bound(x, w, pre):
+    """The split arithmetic's per-element bound on pre = x W^T + b (float64), as in test_linear_split_vs_torch."""
+    return tf.linear(x.double().abs(), w.double().abs()) * 4 * 2.0 ** -22 + 1e-7 * (1 + pre.abs())
+
+
+@pytest.mark.parametrize("m", [1, 255, 256, 257])
+@pytest.mark.parametrize("k,n", [(384, 384), (1536, 384)])
+def test_linear_split_residual_add(lib, m, k, n):
+    """Act 4, y += x W^T + b in place (the backbone's proj and w3: linear_split_kernel<2, 4, 4>, 256-row blocks),
+    against float64 with the split linear's per-row bound; the 1e-7 |ref| term covers the add's one rounding.
+    m = 257 runs with ldy = n + 16."""
+    from genpose2_amd._lib import check
+    from genpose2_amd.fus_encoder import pack_split_linear
+    g = torch.Generator().manual_seed(m + k + n + 4)
+    pad = 16 if m == 257 else 0
+    x = _spread_rows(m, k, g)
+    w = torch.randn(n, k, generator=g) / k ** 0.5
+    b = torch.randn(n, generator=g)
+    y_in = torch.randn(m, n, generator=g)
+    pre = tf.linear(x.double(), w.double(), b.double())
+    ref = y_in.double() + pre
+    xd, wd, bd = x.to(DEV), torch.from_numpy(pack_split_linear(w.numpy())).to(DEV), b.to(DEV)
+    y = torch.zeros(m, n + pad, device=DEV)
+    y[:, :n] = y_in.to(DEV)
+    y2 = y.clone()
+    rmax = torch.full((m,), -1.0, device=DEV)
+    ymax = torch.full((m,), -1.0, device=DEV)
+    check(lib.gp_linear_split(_vp(xd), k, m, k, _vp(wd), _vp(bd), n, 4, _vp(y), n + pad, _vp(rmax), 0, _vp(ymax),
+                              _s()), "linear_split act 4")
+    torch.cuda.synchronize()
+    assert torch.equal(rmax.cpu(), x.abs().max(1).values)
+    assert torch.equal(ymax, y[:, :n].abs().max(1).values)
+    check(lib.gp_linear_split(_vp(xd), k, m, k, _vp(wd), _vp(bd), n, 4, _vp(y2), n + pad, _vp(rmax), 1, None, _s()),
+          "linear_split act 4 (rmax given)")
+    torch.cuda.synchronize()
+    assert torch.equal(y, y2)
+    bound = tf.linear(x.double().abs(), w.double().abs()) * 4 * 2.0 ** -22 + 1e-7 * (1 + ref.abs())
+    err = (y[:, :n].cpu().double() - ref).abs()
+    print(f"linear_split act 4 m={m} k={k}: max err / bound {float((err / bound).max()):.3f}")
+    assert torch.all(err <= bound), float((err / bound).max())
+    if pad:
+        assert torch.all(y[:, n:] == 0)
+
+
+def _swiglu_setup(m, g):
+    from genpose2_amd import dino
+    from genpose2_amd.fus_encoder import pack_split_linear
+    k, h = 384, 1536
+    x = _spread_rows(m, k, g)
+    w1, w2 = torch.randn(h, k, generator=g) / k ** 0.5, torch.randn(h, k, generator=g) / k ** 0.5
+    b1, b2 = torch.randn(h, generator=g), torch.randn(h, generator=g)
+    w = dino.interleave_gate_up(w1.numpy(), w2.numpy())
+    b = dino.interleave_gate_up(b1.numpy(), b2.numpy())
+    return x, (w1, b1, w2, b2), torch.from_numpy(pack_split_linear(w)).to(DEV), torch.from_numpy(b).to(DEV)
+
+
+def _swiglu_check(y_rows, x_rows, wb, tag):
+    """silu(x W1^T + b1) * (x W2^T + b2) in float64 from the un-interleaved halves. With e_g, e_u the linear bound of
+    the gate and the up pre-activation: |err| <= 1.1 |u| e_g + |silu(g)| e_u + e_g e_u + 4e-7 |ref| (|silu'| <= 1.0999;
+    the last term is expf, the divide and the multiply)."""
+    w1, b1, w2, b2 = wb
+    gt = tf.linear(x_rows.double(), w1.double(), b1.double())
+    up = tf.linear(x_rows.double(), w2.double(), b2.double())
+    sg = gt * torch.sigmoid(gt)
+    ref = sg * up
+    e_g, e_u = _linear_bound(x_rows, w1, gt), _linear_bound(x_rows, w2, up)
+    bound = 1.1 * up.abs() * e_g + sg.abs() * e_u + e_g * e_u + 4e-7 * ref.abs()
+    err = (y_rows.cpu().double() - ref).abs()
+    assert bool(torch.isfinite(y_rows).all())
+    print(f"linear_split act 5 {tag}: max err / bound {float((err / bound).max()):.3f}")
+    assert torch.all(err <= bound), float((err / bound).max())
+
+
+@pytest.mark.parametrize("m", [1, 127, 128, 129, 10752, 10753])
+def test_linear_split_swiglu(lib, m):
+    """Act 5, the backbone's w1 | w2 GEMM (k = 384, n = 3072, gate and up interleaved in 16-row tiles) with the row
+    maxima it hands to the w3 GEMM. m <= 10752 runs linear_split_kernel<4, 5, 4> (128-row blocks), m = 10753 is the
+    first size on <4, 5, 8> (256-row blocks; its last block holds one row). The two large m are held to float64 on
+    the first 256, the last 256 and 512 seeded rows; the row maxima are checked exactly on every row. m = 129 runs
+    with ldy = 1536 + 16."""
+    from genpose2_amd._lib import check
+    k, n, h = 384, 3072, 1536
+    g = torch.Generator().manual_seed(m + 5)
+    x, wb, wd, bd = _swiglu_setup(m, g)
+    pad = 16 if m == 129 else 0
+    xd = x.to(DEV)
+    y = torch.full((m, h + pad), 3.0, device=DEV)
+    rmax = torch.full((m,), -1.0, device=DEV)
+    ymax = torch.full((m,), -1.0, device=DEV)
+    check(lib.gp_linear_split(_vp(xd), k, m, k, _vp(wd), _vp(bd), n, 5, _vp(y), h + pad, _vp(rmax), 0, _vp(ymax),
+                              _s()), "linear_split act 5")
+    torch.cuda.synchronize()
+    assert torch.equal(rmax.cpu(), x.abs().max(1).values)
+    assert torch.equal(ymax, y[:, :h].abs().max(1).values)          # exact, every row: what the w3 GEMM scales by
+    if pad:
+        assert torch.all(y[:, h:] == 3.0)
+    if m > 1024:
+        pick = torch.randperm(m, generator=g)[:512]
+        rows = torch.unique(torch.cat([torch.arange(256), torch.arange(m - 256, m), pick]))
+    else:
+        rows = torch.arange(m)
+    _swiglu_check(y[rows.to(DEV), :h], x[rows], wb, f"m={m}")
+    y2 = torch.full_like(y, 3.0)          # the same call with the row maxima of x handed over
+    check(lib.gp_linear_split(_vp(xd), k, m, k, _vp(wd), _vp(bd), n, 5, _vp(y2), h + pad, _vp(rmax), 1, None, _s()),
+          "linear_split act 5 (rmax given)")
+    torch.cuda.synchronize()
+    assert torch.equal(y, y2)
+    if m == 10753:
+        # a row's k-order and scaling do not depend on the tile's row count: the first 128 rows as their own call
+        # (on the 128-row tile) give the same bits as inside the 256-row blocks
+        y3 = torch.full((128, h), 3.0, device=DEV)
+        r3, m3 = torch.empty(128, device=DEV), torch.empty(128, device=DEV)
+        check(lib.gp_linear_split(_vp(xd), k, 128, k, _vp(wd), _vp(bd), n, 5, _vp(y3), h, _vp(r3), 0, _vp(m3), _s()),
+              "linear_split act 5 (128 rows)")
+        torch.cuda.synchronize()
+        assert torch.equal(y3, y[:128]) and torch.equal(m3, ymax[:128])
+
+
+def test_linear_split_swiglu_refuses_unpaired_tiles(lib):
+    """n = 48 (not a multiple of 32) leaves a gate tile without its up tile: a non-zero code, nothing written."""
+    k = 384
+    x = torch.randn(8, k, device=DEV)
+    wd = torch.zeros(int(lib.gp_linear_split_words(48, k)), dtype=torch.int32, device=DEV)
+    bd = torch.zeros(128, device=DEV)
+    y, rmax, ymax = (torch.full(s, 3.0, device=DEV) for s in ((8, 128), (8,), (8,)))
+    rc = lib.gp_linear_split(_vp(x), k, 8, k, _vp(wd), _vp(bd), 48, 5, _vp(y), 128, _vp(rmax), 0, _vp(ymax), _s())
+    torch.cuda.synchronize()
+    assert rc != 0 and b"multiple of 32" in lib.gp_last_error()
+    assert bool((y == 3.0).all()) and bool((rmax == 3.0).all()) and bool((ymax == 3.0).all())
+
+
 def test_add_layernorm_vs_torch(lib):
     from genpose2_amd._lib import check
     for m, d in ((777, 96), (300, 1024), (5, 512), (64, 256)):
