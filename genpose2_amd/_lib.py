@@ -146,6 +146,25 @@ _SIGS: Dict[str, tuple] = {
                              ctypes.c_longlong, c_void_p, c_void_p]),
     "gp_ode_denoise": (c_int, [ctypes.POINTER(HeadWeights), c_void_p, c_float, c_float, c_float, c_float, c_void_p,
                                c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    # the energy agent's ODE entries: their namesakes' arguments with the transposed weights behind w
+    "gp_ode_rhs_energy": (c_int, [ctypes.POINTER(HeadWeights), ctypes.POINTER(HeadGradWeights), c_void_p, c_float,
+                                  c_float, c_double, c_void_p, c_void_p, c_void_p, c_int, c_double, c_int, c_int,
+                                  c_void_p, c_void_p, c_size_t, c_void_p]),
+    "gp_ode_attempt_energy": (c_int, [ctypes.POINTER(HeadWeights), ctypes.POINTER(HeadGradWeights), c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_double,
+                                      c_double, c_double, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
+                                      c_void_p]),
+    "gp_ode_auto_attempt_energy": (c_int, [ctypes.POINTER(HeadWeights), ctypes.POINTER(HeadGradWeights), c_void_p,
+                                           c_int, c_int, c_double, c_double, c_double, c_double, c_double, c_double,
+                                           c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                           c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "gp_ode_denoise_energy": (c_int, [ctypes.POINTER(HeadWeights), ctypes.POINTER(HeadGradWeights), c_void_p, c_float,
+                                      c_float, c_float, c_float, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                      c_void_p, c_size_t, c_void_p]),
+    "gp_ode_sample_energy": (c_int, [ctypes.POINTER(HeadWeights), ctypes.POINTER(HeadGradWeights), c_void_p, c_void_p,
+                                     c_int, c_int, c_double, c_double, c_int, c_double, c_double, c_void_p, c_void_p,
+                                     c_void_p, ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_void_p, c_size_t,
+                                     c_void_p]),
     "gp_ode_ctl_size": (c_size_t, []),
     "gp_ode_auto_workspace_size": (c_size_t, [c_int]),
     "gp_ode_auto_attempt": (c_int, [ctypes.POINTER(HeadWeights), c_void_p, c_int, c_int, c_double, c_double, c_double,

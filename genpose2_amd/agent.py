@@ -244,8 +244,13 @@ class PoseNet:
             raise NotImplementedError("pred_func needs agent_type='score' or 'energy'")
         energy_grad = self.cfg.agent_type == "energy"   # the score is the energy's gradient (energynet.py:211-233)
         if energy_grad and self.cfg.sampler_mode[0] == "ode":
-            raise NotImplementedError("the ODE sampler is not built for agent_type='energy' (the energy gradient "
-                                      "drives the PC sampler only)")
+            if not self.cfg.energy_ode:
+                raise NotImplementedError("the ODE sampler runs agent_type='energy' only with "
+                                          "GenPoseConfig.energy_ode=True (off by default: the energy's gradient is "
+                                          "discontinuous at ReLU kinks, which costs RK45 evaluations and accuracy)")
+            if self.cfg.ode_coupling == "object":
+                raise NotImplementedError("ode_coupling='object' is not built for agent_type='energy' (the energy "
+                                          "agent's ODE solve is whole-batch)")
         if energy_grad and self.global_batch is not None:
             raise NotImplementedError("global-batch sampling is not built for agent_type='energy'")
         coupling = self.cfg.pc_coupling
@@ -320,7 +325,7 @@ class PoseNet:
             in_process = xs.view(bs, K, T, -1) if xs is not None else None
         elif mode == "ode":
             pred_pose, pred_q, in_process = self._ode(pobj, center, bs, K, rep_init, T0,
-                                                      bool(return_process or self.cfg.save_video))
+                                                      bool(return_process or self.cfg.save_video), energy_grad)
         else:
             raise NotImplementedError(mode)
         self.pts_feature = False
@@ -335,10 +340,11 @@ class PoseNet:
             return [pred_pose, in_process]
         return pred_pose, pred_q
 
-    def _ode(self, pobj, center, bs, K, rep_init, T0, want_process=False):
+    def _ode(self, pobj, center, bs, K, rep_init, T0, want_process=False, energy_grad=False):
         """cond_ode_sampler (samplers.py:180-258) on device: RK45 stages, error norms and dense
         output are HIP launches (genpose2_amd/ode.py DeviceRk45); the controller runs scipy's step
-        logic on host scalars. Returns (pose (B,K,9) fp64, q (B,K,7) fp64, process or None)."""
+        logic on host scalars. energy_grad: the score is the energy model's gradient (the energy backend of
+        DeviceRk45, whole-batch coupling). Returns (pose (B,K,9) fp64, q (B,K,7) fp64, process or None)."""
         R = bs * K
         T0 = arch.SDE_T if T0 is None else float(T0)
         eps = arch.SAMPLING_EPS
@@ -381,7 +387,7 @@ class PoseNet:
                 raise RuntimeError("global-batch RK45 failed (step size below the spacing of t) with t_eval set: the "
                                    "t_eval outputs collected before the failure need the host controller")
         else:
-            be = DeviceRk45(self.heads, pobj, x0.to(self.device), K)
+            be = DeviceRk45(self.heads, pobj, x0.to(self.device), K, energy_grad=energy_grad)
             if want_process or self.ode_host_control or self.ode_trace is not None:
                 # every solve_ivp output is kept: host-side controller, one error norm read per attempt
                 _, nfev, status = rk45_drive(be, T0, eps, t_eval=t_eval, keep_all=want_process,
@@ -392,7 +398,7 @@ class PoseNet:
             if status < 0 and t_eval is not None and not want_process:
                 # failed solve (step below spacing): solve_ivp returns the t_eval points collected so far and
                 # cond_ode_sampler continues from res.y[:, -1]; only the host restatement keeps them all
-                be = DeviceRk45(self.heads, pobj, x0.to(self.device), K)
+                be = DeviceRk45(self.heads, pobj, x0.to(self.device), K, energy_grad=energy_grad)
                 _, nfev, status = rk45_drive(be, T0, eps, t_eval=t_eval, keep_all=True)
                 want_process = False
             if (want_process or self.ode_host_control or self.ode_trace is not None
@@ -413,7 +419,7 @@ class PoseNet:
             step = float(np.float32((1 - eps) / (1000 if steps is None else steps)))
             sc = self._denoise_scalars[key] = (t32, sig, g2, step)
         t32, sig, g2, step = sc
-        pose, q = self.heads.ode_denoise(pobj, t32, sig, g2, step, x, K, center, be.ws)
+        pose, q = self.heads.ode_denoise(pobj, t32, sig, g2, step, x, K, center, be.ws, energy_grad=energy_grad)
         in_process = None
         if want_process:
             n_t = ys.shape[0]

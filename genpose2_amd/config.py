@@ -53,6 +53,11 @@ class GenPoseConfig:
     # takes its error norms over: batch (one solve_ivp on every row of the call, as the reference's evaluation
     # calls cond_ode_sampler) | object (one solve per object: its own steps, accept / reject and nfev)
     ode_coupling: str = "batch"
+    # agent_type "energy" with the ODE sampler: the energy's gradient as the probability-flow ODE's score, as the
+    # reference's cond_ode_sampler runs either agent (read only then). Off by default: the gradient is
+    # discontinuous at ReLU kinks, so RK45 takes more evaluations than with the ScoreNet and is accurate to about
+    # 1e-3 only (DESIGN "Energy agent on the ODE sampler"); whole-batch coupling only
+    energy_ode: bool = False
 
     def copy(self, **kw) -> "GenPoseConfig":
         return replace(self, **kw)
@@ -82,3 +87,5 @@ class GenPoseConfig:
             raise ValueError(f"pc_coupling {self.pc_coupling!r} (batch | object)")
         if self.ode_coupling not in ("batch", "object"):
             raise ValueError(f"ode_coupling {self.ode_coupling!r} (batch | object)")
+        if not isinstance(self.energy_ode, bool):
+            raise ValueError(f"energy_ode {self.energy_ode!r} (True | False)")

@@ -10,7 +10,8 @@
 // (_estimate_error_norm, rk.py); ode_norm_kernel reduces it in a fixed order. The step
 // controller's scalars stay on the host (genpose2_amd/ode.py): one 8-byte read per attempt. The
 // device-controlled attempts (gp_ode_auto_attempt) run all six stages of an attempt in one launch
-// (ode_attempt_kernel); the host-controlled ones launch each stage (ode_stage_kernel).
+// (ode_attempt_kernel); the host-controlled ones launch each stage (ode_stage_kernel). What the energy agent's
+// stages (gp_ode_energy.hip) share with these is declared in gp_ode.h.
 #include <chrono>
 #include <cstddef>
 #include <cstdlib>
@@ -18,93 +19,7 @@
 #include <utility>
 #include <vector>
 
-#include "gp_head.h"
-
-#define ODE_NK 7   // Dormand-Prince stages incl. the FSAL derivative
-
-// Device-resident RK45 controller state (the device-controlled path, gp_ode_auto_*). One copy per
-// attempt parity: the control kernel of attempt n reads ctl[n & 1] and writes ctl[(n + 1) & 1], the
-// stage kernels of attempt n read ctl[(n + 1) & 1]. Field order fixed (doubles, floats, ints) so the
-// host mirror (genpose2_amd/ode.py OdeCtl) has the same layout.
-struct OdeCtl {
-    double t, h_abs;              // solver time; step size carried to the next step (scipy self.h_abs)
-    double t_old, h_last;         // last accepted step (dense output)
-    double h, t_new, h_abs_loc;   // the prepared attempt (scipy _step_impl locals h, t_new, h_abs)
-    double coef[6];               // -(0.5 g(t_s)^2) of the attempt's 6 stage times
-    float t32[6], sig[6];         // float32(t_s), sigma(t32)
-    int status;                   // 0 running, 1 finished, -1 step size below spacing (scipy failure)
-    int active;                   // the prepared attempt runs
-    int rejected;                 // scipy step_rejected within the current step
-    int nfev, n_acc, yi;          // RHS evaluations, accepted steps, y buffer holding the state
-    int kidx[ODE_NK];             // K slot permutation (FSAL swaps slots 0 and 6 on acceptance)
-};
-static_assert(sizeof(OdeCtl) == 208, "OdeCtl layout is mirrored on the host");
-
-struct OdeStageArgs {
-    gp_head_weights w;
-    const float* pobj;
-    const float* tproj;          // (768) time row of this stage's t (host-controlled calls)
-    float sigma;                 // sigma(t32), fp32 (score = f / (sigma + 1e-7))
-    double coef;                 // -(0.5 * g(t)^2)
-    const double* y;             // (R,9) state at the step's start
-    const double* k[ODE_NK];     // stage derivatives combined into this stage's input
-    double a[ODE_NK];            // y_in = y + (sum_{j<nk} a_j K_j) * h
-    int nk;
-    double h;
-    double* kout;                // (R,9) this stage's derivative
-    // final stage of an attempt (MODE 1): y_new out and the error-estimator partials
-    double* ynew;
-    double e[ODE_NK];            // error weights over K_0..K_6 (K_6 = this stage)
-    double rtol, atol;
-    double* part;                // (nwg) sum over the workgroup's elements of (err/scale)^2
-    int part_off;                // index of this launch's first partial (global-batch shards: the single call's
-                                 // workgroup index of this shard's first row tile; 0 otherwise)
-    int rows, kper;
-    // device-controlled attempts: state, time rows and buffers resolved from ctl
-    const OdeCtl* ctl;           // null for host-controlled calls
-    const float* tproj6;         // (6,768) rows of the prepared attempt
-    double* ybuf[2];
-    double* kbuf[ODE_NK];
-    int stage;                   // 1..6
-};
-
-// The stage arithmetic the sampler's and the likelihood's stage kernels share, one definition each: a last-bit
-// difference in any of them can flip an accept / reject of the step controller.
-// y_in = y + (sum_{j<nk} a_j K_j) h of entry e, nk >= 1 (scipy rk.py rk_step's order)
-__device__ __forceinline__ double ode_stage_in(const double* const* kin, const double* acoef, int nk, double h, size_t e,
-                                               double yv) {
-#pragma clang fp contract(off)
-    double acc = kin[0][e] * acoef[0];
-    for (int s = 1; s < nk; ++s) acc = acc + kin[s][e] * acoef[s];
-    return yv + acc * h;
-}
-// scipy's error term of entry e: err = (K^T E) h / scale, scale = atol + max(|y|, |y_new|) rtol; kv = K_6[e], the
-// derivative this stage just formed
-template <typename Args>   // OdeStageArgs, or the per-object OdeObjArgs (e, atol, rtol)
-__device__ __forceinline__ double ode_err_term(const Args& a, const double* const* kin, double kv, double h,
-                                               size_t e, double y0, double y1) {
-#pragma clang fp contract(off)
-    double acc = kin[0][e] * a.e[0];
-    for (int s = 1; s < ODE_NK - 1; ++s) acc = acc + kin[s][e] * a.e[s];
-    acc = acc + kv * a.e[ODE_NK - 1];
-    const double sc = a.atol + fmax(fabs(y0), fabs(y1)) * a.rtol;
-    return (acc * h) / sc;
-}
-// The workgroup's sum of the threads' sq in a fixed order (xor tree per wave, waves in order) -> *out; esq: one
-// double of LDS per wave
-__device__ __forceinline__ void ode_block_partial(double sq, double* esq, double* out) {
-#pragma clang fp contract(off)
-    const int tid = threadIdx.x;
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) sq += __shfl_xor(sq, off, 64);
-    if ((tid & 63) == 0) esq[tid >> 6] = sq;
-    __syncthreads();
-    if (tid == 0) {
-        double t = 0.0;
-        for (int v = 0; v < EVAL_WV; ++v) t += esq[v];
-        *out = t;
-    }
-}
+#include "gp_ode.h"
 
 // One RK45 stage for the workgroup's rows. MODE 0: stage derivative. MODE 1: last stage of an attempt
 // (y_new, K_6, error partials). y_in = y + (sum_{j<nk} acoef_j K_j) h, K_out = coef * score(f32(y_in), t).
@@ -200,9 +115,6 @@ __global__ __launch_bounds__(EVAL_WV * 64) void ode_stage_kernel(OdeStageArgs a)
 // without five kernel boundaries (each ~3 us of tail, boundary and refill at config 4). The K_s a stage
 // writes are read back by other threads of the workgroup after the stage's barrier (the workgroup-scope
 // release / acquire of __syncthreads orders the global stores before those loads).
-struct OdeTableau {
-    double A[36], B[6];
-};
 template <int PL, int NT>
 __global__ __launch_bounds__(EVAL_WV * 64) void ode_attempt_kernel(OdeStageArgs a, OdeTableau tb) {
     constexpr int ROWS = 16 * NT;
@@ -493,19 +405,6 @@ __global__ __launch_bounds__(256) void ode_dense_kernel(OdeDenseArgs a) {
 // mean_x = x + (0 - g^2 grad) * c (fp32 product, fp64 sum), then GS of [:6], + pts_center, quaternion
 // (posenet_agent.py:554-556). Writes pose (R,9) fp64 and q (R,7) fp64. The score runs on the stage kernels'
 // trunk and tile (f16x3, 64 candidates per workgroup at R >= 8193; exact fp32 without the f16 planes).
-struct OdeDenoiseArgs {
-    gp_head_weights w;
-    const float* pobj;
-    const float* tproj;
-    float sigma;
-    float g2;        // diffusion(eps)^2 in fp32
-    float step;      // (1 - eps) / num_steps as fp32
-    const double* x;
-    const float* center;
-    double* pose;
-    double* q;
-    int rows, kper;
-};
 
 template <int PL, int NT>   // PL 0: exact fp32 trunk, X3P: f16x3 (the stage kernels' arithmetic)
 __global__ __launch_bounds__(EVAL_WV * 64) void ode_denoise_kernel(OdeDenoiseArgs a) {
@@ -571,18 +470,23 @@ __global__ __launch_bounds__(HT) void ode_time_rows_kernel(gp_head_weights w, Od
 
 // ------------------------------------------------------------------------------ C ABI
 // Workspace: 6 time rows (6 x 768 fp32) | per-workgroup error partials (fp64).
-static size_t ode_part_offset() { return 6 * 768 * sizeof(float); }
+size_t ode_part_offset() { return 6 * 768 * sizeof(float); }
 
 extern "C" size_t gp_ode_workspace_size(int rows) {
     return ode_part_offset() + sizeof(double) * (((size_t)rows + 15) / 16) + 256;
 }
 
-static int ode_launch_times(const gp_head_weights* w, const float* t32, int nt, void* ws, hipStream_t stream) {
+int ode_launch_times(const gp_head_weights* w, const float* t32, int nt, void* ws, hipStream_t stream) {
     OdeTimes tv = {};
     for (int i = 0; i < nt; ++i) tv.t[i] = t32[i];
     hipLaunchKernelGGL(ode_time_rows_kernel, dim3(nt, ODE_ROW_CHUNKS), dim3(HT), 0, stream, *w, tv,
                        static_cast<float*>(ws));
     return gp_check_launch("ode_time_rows_kernel");
+}
+
+int ode_launch_norm(const double* part, int n, double count, double* out, hipStream_t stream) {
+    hipLaunchKernelGGL(ode_norm_kernel, dim3(1), dim3(256), 0, stream, part, n, count, out);
+    return gp_check_launch("ode_norm_kernel");
 }
 
 extern "C" int gp_ode_rhs(const gp_head_weights* w, const float* pobj, float t32, float sigma, double coef,
@@ -961,7 +865,7 @@ static int ode_auto_attempt_impl(const gp_head_weights* w, const float* pobj, in
                                  double diff_scale, double* y0, double* y1, double* const* kslots,
                                  const double* tableau_a, const double* b, const double* e, int rows, int k,
                                  const OdeGlobal* g, void* workspace, size_t workspace_bytes, int* hstat,
-                                 hipStream_t stream) {
+                                 hipStream_t stream, const gp_head_grad_weights* gw = nullptr) {
     GP_REQUIRE(w && pobj && y0 && y1 && kslots && tableau_a && b && e && workspace && rows >= 1 && k >= 1 && n >= 0,
                "ode_auto_attempt: bad arguments");
     for (int j = 0; j < ODE_NK; ++j) GP_REQUIRE(kslots[j] != nullptr, "ode_auto_attempt: null K slot");
@@ -969,7 +873,8 @@ static int ode_auto_attempt_impl(const gp_head_weights* w, const float* pobj, in
     OdeCtl* ctl = reinterpret_cast<OdeCtl*>(ws);
     float* tproj6 = reinterpret_cast<float*>(ws + auto_tproj_off());
     double* part = reinterpret_cast<double*>(ws + auto_part_off());
-    const int nt = ode_nt(w, g ? g->rows_total : rows);
+    // gw: the energy agent's stages (gp_ode_energy.hip), 16-row tiles whatever the trunk arithmetic of w
+    const int nt = gw ? 1 : ode_nt(w, g ? g->rows_total : rows);
     const int nwg = (rows + 16 * nt - 1) / (16 * nt);   // this call's workgroups
     const int part_n = g ? g->part_n : nwg;
     GP_REQUIRE(!g || (g->part_off >= 0 && g->part_off + nwg <= part_n),
@@ -1006,6 +911,7 @@ static int ode_auto_attempt_impl(const gp_head_weights* w, const float* pobj, in
         for (int j = 0; j < 6; ++j) tb.B[j] = b[j];
         for (int j = 0; j < ODE_NK; ++j) a.e[j] = e[j];
         a.part = part;
+        if (gw) return ode_energy_launch_attempt(a, *gw, tb, stream);
         const dim3 grid(nwg), blk(EVAL_WV * 64);
         head_dispatch(w->pe2_h ? X3P : 0, nt, [&](auto pl, auto ntc) {
             hipLaunchKernelGGL((ode_attempt_kernel<pl.value, ntc.value>), grid, blk, 0, stream, a, tb);
@@ -1020,13 +926,19 @@ static int ode_auto_attempt_impl(const gp_head_weights* w, const float* pobj, in
         a.stage = s;
         a.nk = s;
         for (int j = 0; j < s; ++j) a.a[j] = tableau_a[s * 6 + j];
-        ode_launch_stage<0>(a, nt, stream);
+        if (gw) {
+            const int rc = ode_energy_launch_stage(a, *gw, false, stream);
+            if (rc) return rc;
+        } else {
+            ode_launch_stage<0>(a, nt, stream);
+        }
     }
     a.stage = 6;
     a.nk = 6;
     for (int j = 0; j < 6; ++j) a.a[j] = b[j];
     for (int j = 0; j < ODE_NK; ++j) a.e[j] = e[j];
     a.part = part;
+    if (gw) return ode_energy_launch_stage(a, *gw, true, stream);
     ode_launch_stage<1>(a, nt, stream);
     const int rc = gp_check_launch("ode_stage_kernel<auto>");
     if (rc || !g) return rc;
@@ -1054,6 +966,18 @@ extern "C" int gp_ode_auto_attempt_hs(const gp_head_weights* w, const float* pob
     return ode_auto_attempt_impl(w, pobj, n, what, t_bound, direction, rtol, atol, sig_min, base, diff_scale, y0, y1,
                                  kslots, tableau_a, b, e, rows, k, nullptr, workspace, workspace_bytes, host_status,
                                  stream);
+}
+
+extern "C" int gp_ode_auto_attempt_energy(const gp_head_weights* w, const gp_head_grad_weights* gw, const float* pobj,
+                                          int n, int what, double t_bound, double direction, double rtol,
+                                          double atol, double sig_min, double base, double diff_scale, double* y0,
+                                          double* y1, double* const* kslots, const double* tableau_a,
+                                          const double* b, const double* e, int rows, int k, void* workspace,
+                                          size_t workspace_bytes, int* host_status, hipStream_t stream) {
+    GP_REQUIRE(ode_energy_weights_ok(gw), "ode_auto_attempt_energy: null transposed weights");
+    return ode_auto_attempt_impl(w, pobj, n, what, t_bound, direction, rtol, atol, sig_min, base, diff_scale, y0, y1,
+                                 kslots, tableau_a, b, e, rows, k, nullptr, workspace, workspace_bytes, host_status,
+                                 stream, gw);
 }
 
 extern "C" int gp_ode_global_partials(int rows_total, int shard_rows_max, int shards, int split) {
@@ -1200,10 +1124,12 @@ __global__ void f32_to_f64_kernel(const float* __restrict__ in, double* __restri
 
 extern "C" size_t gp_ode_sample_workspace_size(int rows) { return rows >= 1 ? ode_sample_layout(rows).total : 0; }
 
-extern "C" int gp_ode_sample(const gp_head_weights* w, const float* pobj, const float* x0, int rows, int k, double T0,
-                             double eps, int steps, double rtol, double atol, const float* pts_center, double* pose,
-                             double* q, int* nfev_out, int* status_out, void* workspace, size_t workspace_bytes,
-                             hipStream_t stream) {
+// gw: null for the score agent; the energy agent's transposed weights otherwise (its right-hand sides, attempts
+// and denoise are gp_ode_rhs_energy, gp_ode_auto_attempt_energy and gp_ode_denoise_energy)
+static int ode_sample_impl(const gp_head_weights* w, const gp_head_grad_weights* gw, const float* pobj,
+                           const float* x0, int rows, int k, double T0, double eps, int steps, double rtol,
+                           double atol, const float* pts_center, double* pose, double* q, int* nfev_out,
+                           int* status_out, void* workspace, size_t workspace_bytes, hipStream_t stream) {
     GP_REQUIRE(w && pobj && x0 && pts_center && pose && q && workspace && rows >= 1 && k >= 1 && steps >= 0,
                "ode_sample: bad arguments");
     GP_REQUIRE(T0 != eps, "ode_sample: empty integration interval (T0 == eps)");
@@ -1226,6 +1152,13 @@ extern "C" int gp_ode_sample(const gp_head_weights* w, const float* pobj, const 
     const double t0 = T0, tf = eps, dir = tf > t0 ? 1.0 : -1.0;
     const double dscale = diff_scale();
     int rc;
+    auto rhs = [&](float t32, double coef, const double* const* kin, const double* acoef, int nk, double h,
+                   double* kout) {
+        return gw ? gp_ode_rhs_energy(w, gw, pobj, t32, sigma32(t32), coef, y[0], kin, acoef, nk, h, rows, k, kout,
+                                      rws, rws_b, stream)
+                  : gp_ode_rhs(w, pobj, t32, sigma32(t32), coef, y[0], kin, acoef, nk, h, rows, k, kout, rws, rws_b,
+                               stream);
+    };
     hipLaunchKernelGGL(f32_to_f64_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, x0, y[0], n);
     if ((rc = gp_check_launch("f32_to_f64_kernel"))) return rc;
 
@@ -1233,9 +1166,7 @@ extern "C" int gp_ode_sample(const gp_head_weights* w, const float* pobj, const 
     {   // f(t0): solve_ivp hands t0 as a Python float, so ode_func's g is float32 sigma * float64 scale
         const float t32 = (float)t0;
         const double g = (double)sigma32(t32) * dscale;
-        if ((rc = gp_ode_rhs(w, pobj, t32, sigma32(t32), -(0.5 * (g * g)), y[0], nullptr, nullptr, 0, 0.0, rows, k,
-                             K[0], rws, rws_b, stream)))
-            return rc;
+        if ((rc = rhs(t32, -(0.5 * (g * g)), nullptr, nullptr, 0, 0.0, K[0]))) return rc;
     }
     if ((rc = gp_ode_init_norms(y[0], K[0], nullptr, n, atol, rtol, scal, stream))) return rc;
     double hs[3];
@@ -1249,9 +1180,7 @@ extern "C" int gp_ode_sample(const gp_head_weights* w, const float* pobj, const 
         const double g = kSigMin * pow(kBase, t) * dscale;
         const double a1 = 1.0;
         const double* kin[1] = {K[0]};
-        if ((rc = gp_ode_rhs(w, pobj, (float)t, sigma32((float)t), -(0.5 * (g * g)), y[0], kin, &a1, 1, h0 * dir,
-                             rows, k, f1, rws, rws_b, stream)))
-            return rc;
+        if ((rc = rhs((float)t, -(0.5 * (g * g)), kin, &a1, 1, h0 * dir, f1))) return rc;
     }
     if ((rc = gp_ode_init_norms(y[0], K[0], f1, n, atol, rtol, scal, stream))) return rc;
     GP_REQUIRE(hipMemcpyAsync(hs + 2, scal + 2, sizeof(double), hipMemcpyDeviceToHost, stream) == hipSuccess &&
@@ -1269,8 +1198,8 @@ extern "C" int gp_ode_sample(const gp_head_weights* w, const float* pobj, const 
     GP_REQUIRE(hipMemcpyAsync(aws, &c0, sizeof(OdeCtl), hipMemcpyHostToDevice, stream) == hipSuccess &&
                    hipStreamSynchronize(stream) == hipSuccess, "ode_sample: controller record");
     auto launch = [&](int a, int what) {
-        return gp_ode_auto_attempt(w, pobj, a, what, tf, dir, rtol, atol, kSigMin, kBase, dscale, y[0], y[1], K,
-                                   kA6, kB6, kE7, rows, k, aws, aws_b, stream);
+        return ode_auto_attempt_impl(w, pobj, a, what, tf, dir, rtol, atol, kSigMin, kBase, dscale, y[0], y[1], K,
+                                     kA6, kB6, kE7, rows, k, nullptr, aws, aws_b, nullptr, stream, gw);
     };
     const int rec = (int)sizeof(OdeCtl);
     const int stat_off = (int)offsetof(OdeCtl, status);
@@ -1286,8 +1215,8 @@ extern "C" int gp_ode_sample(const gp_head_weights* w, const float* pobj, const 
         volatile int* hv = status.r.pinned;
         for (int i = 0; i < 4; ++i) hv[i] = -1;
         auto launch_hs = [&](int n) {
-            return gp_ode_auto_attempt_hs(w, pobj, n, 3, tf, dir, rtol, atol, kSigMin, kBase, dscale, y[0], y[1], K,
-                                          kA6, kB6, kE7, rows, k, aws, aws_b, hs_dev, stream);
+            return ode_auto_attempt_impl(w, pobj, n, 3, tf, dir, rtol, atol, kSigMin, kBase, dscale, y[0], y[1], K,
+                                         kA6, kB6, kE7, rows, k, nullptr, aws, aws_b, hs_dev, stream, gw);
         };
         status.pending = true;   // the device writes the words until the stream drains
         if ((rc = launch_hs(0))) return rc;
@@ -1342,7 +1271,27 @@ extern "C" int gp_ode_sample(const gp_head_weights* w, const float* pobj, const 
     const float sig = sigma32(te);
     const float g = sig * (float)dscale;
     const float step = (float)((1.0 - eps) / (steps > 0 ? steps : 1000));
+    if (gw)
+        return gp_ode_denoise_energy(w, gw, pobj, te, sig, g * g, step, x, rows, k, pts_center, pose, q, rws, rws_b,
+                                     stream);
     return gp_ode_denoise(w, pobj, te, sig, g * g, step, x, rows, k, pts_center, pose, q, rws, rws_b, stream);
+}
+
+extern "C" int gp_ode_sample(const gp_head_weights* w, const float* pobj, const float* x0, int rows, int k, double T0,
+                             double eps, int steps, double rtol, double atol, const float* pts_center, double* pose,
+                             double* q, int* nfev_out, int* status_out, void* workspace, size_t workspace_bytes,
+                             hipStream_t stream) {
+    return ode_sample_impl(w, nullptr, pobj, x0, rows, k, T0, eps, steps, rtol, atol, pts_center, pose, q, nfev_out,
+                           status_out, workspace, workspace_bytes, stream);
+}
+
+extern "C" int gp_ode_sample_energy(const gp_head_weights* w, const gp_head_grad_weights* gw, const float* pobj,
+                                    const float* x0, int rows, int k, double T0, double eps, int steps, double rtol,
+                                    double atol, const float* pts_center, double* pose, double* q, int* nfev_out,
+                                    int* status_out, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+    GP_REQUIRE(ode_energy_weights_ok(gw), "ode_sample_energy: null transposed weights");
+    return ode_sample_impl(w, gw, pobj, x0, rows, k, T0, eps, steps, rtol, atol, pts_center, pose, q, nfev_out,
+                           status_out, workspace, workspace_bytes, stream);
 }
 
 // ============================================================================ per-object RK45 (gp_ode_sample_object)

@@ -464,14 +464,38 @@ class HeadModel:
             self._s()), "ode_sample_object")
         return pose, q, nfev, status
 
+    def ode_sample_energy(self, pobj, x0: torch.Tensor, k: int, pts_center: torch.Tensor, T0: float, eps: float,
+                          steps: Optional[int], rtol: float = 1e-5, atol: float = 1e-5):
+        """cond_ode_sampler driven by the energy model's score, the whole sampler in the one C call
+        (gp_ode_sample_energy, the entry of hosts without Python): x0 (R,9) fp32, the prior sample [+ init_x] at T0
+        -> pose (R,9), q (R,7) fp64, nfev, status (1 done, -1 step size below the spacing of t)."""
+        R = x0.shape[0]
+        x0 = x0.to(self.device, torch.float32).contiguous()
+        ws = torch.empty(int(self.lib.gp_ode_sample_workspace_size(R)), dtype=torch.uint8, device=self.device)
+        pose = torch.empty((R, arch.POSE_DIM), dtype=torch.float64, device=self.device)
+        q = torch.empty((R, 7), dtype=torch.float64, device=self.device)
+        nfev, status = ctypes.c_int(0), ctypes.c_int(0)
+        check(self.lib.gp_ode_sample_energy(
+            ctypes.byref(self.w), ctypes.byref(self.grad_weights), ctypes.c_void_p(pobj.data_ptr()),
+            ctypes.c_void_p(x0.data_ptr()), R, k, float(T0), float(eps), 0 if steps is None else int(steps),
+            float(rtol), float(atol), ctypes.c_void_p(require_device_tensor(pts_center, "pts_center").data_ptr()),
+            ctypes.c_void_p(pose.data_ptr()), ctypes.c_void_p(q.data_ptr()), ctypes.byref(nfev), ctypes.byref(status),
+            ctypes.c_void_p(ws.data_ptr()), ws.numel(), self._s()), "ode_sample_energy")
+        return pose, q, int(nfev.value), int(status.value)
+
     def ode_denoise(self, pobj, t32: float, sigma: float, g2: float, step: float, x: torch.Tensor, k: int,
-                    pts_center: torch.Tensor, ws: torch.Tensor):
-        """cond_ode_sampler's final denoise + epilogue (gp_ode_denoise) -> pose (R,9), q (R,7) fp64."""
+                    pts_center: torch.Tensor, ws: torch.Tensor, energy_grad: bool = False):
+        """cond_ode_sampler's final denoise + epilogue (gp_ode_denoise) -> pose (R,9), q (R,7) fp64.
+        ``energy_grad``: gp_ode_denoise_energy, the step's score is the energy model's gradient."""
         R = x.numel() // arch.POSE_DIM
         pose = torch.empty((R, arch.POSE_DIM), dtype=torch.float64, device=self.device)
         q = torch.empty((R, 7), dtype=torch.float64, device=self.device)
-        check(self.lib.gp_ode_denoise(
-            ctypes.byref(self.w), ctypes.c_void_p(pobj.data_ptr()), t32, sigma, g2, step,
+        if energy_grad:
+            fn, head = self.lib.gp_ode_denoise_energy, (ctypes.byref(self.w), ctypes.byref(self.grad_weights))
+        else:
+            fn, head = self.lib.gp_ode_denoise, (ctypes.byref(self.w),)
+        check(fn(
+            *head, ctypes.c_void_p(pobj.data_ptr()), t32, sigma, g2, step,
             ctypes.c_void_p(x.data_ptr()), R, k, ctypes.c_void_p(require_device_tensor(pts_center, "pts_center").data_ptr()),
             ctypes.c_void_p(pose.data_ptr()), ctypes.c_void_p(q.data_ptr()), ctypes.c_void_p(ws.data_ptr()),
             ws.numel(), self._s()), "ode_denoise")

@@ -105,6 +105,8 @@ def rk45_drive(be, t0: float, t_bound: float, rtol: float = 1e-5, atol: float = 
             t_eval_i = t_eval.shape[0]
         be.set_t_eval(np.ascontiguousarray(t_eval), direction, keep_all)
     h_abs, nfev = initial_step(be, t0, tf, direction)
+    # error_norm ** ERROR_EXPONENT: NumPy's power, or the backend's own (DeviceRk45's energy backend: the device's)
+    err_pow = getattr(be, "err_pow", None) or (lambda e: e ** ERROR_EXPONENT)
     ts: List[float] = [t0] if t_eval is None else []
     if t_eval is None:
         be.keep_y(keep_all, first=True)
@@ -139,13 +141,13 @@ def rk45_drive(be, t0: float, t_bound: float, rtol: float = 1e-5, atol: float = 
                 if error_norm == 0:
                     factor = MAX_FACTOR
                 else:
-                    factor = min(MAX_FACTOR, SAFETY * error_norm ** ERROR_EXPONENT)
+                    factor = min(MAX_FACTOR, SAFETY * err_pow(error_norm))
                 if step_rejected:
                     factor = min(1, factor)
                 h_abs *= factor
                 step_accepted = True
             else:
-                h_abs *= max(MIN_FACTOR, SAFETY * error_norm ** ERROR_EXPONENT)
+                h_abs *= max(MIN_FACTOR, SAFETY * err_pow(error_norm))
                 step_rejected = True
         if failed:
             # solve_ivp returns (status -1) with the outputs collected so far; the reference then
@@ -284,12 +286,17 @@ def stage_scalars(ts: List[float]):
 
 
 class DeviceRk45:
-    """State y, K_0..K_6 and y_new as fp64 (R*9) device tensors; every RHS is a HIP launch."""
+    """State y, K_0..K_6 and y_new as fp64 (R*9) device tensors; every RHS is a HIP launch. ``energy_grad``: the
+    energy agent's backend -- the score of every right-hand side is the energy's gradient (gp_ode_rhs_energy,
+    gp_ode_attempt_energy; rk45_device then runs gp_ode_auto_attempt_energy), the rest is shared."""
 
     def __init__(self, heads, pobj: torch.Tensor, y0: torch.Tensor, k: int, rtol: float = 1e-5,
-                 atol: float = 1e-5):
+                 atol: float = 1e-5, energy_grad: bool = False):
         self.lib = _lib.load()
         self.h = heads
+        self.energy_grad = bool(energy_grad)
+        if self.energy_grad:   # rk45_drive's step-size factor with the device's pow, as _device_stage_scalars
+            self.err_pow = self._device_err_pow
         self.dev = heads.device
         self.pobj = pobj
         self.R = y0.numel() // arch.POSE_DIM
@@ -314,10 +321,38 @@ class DeviceRk45:
         nk = len(kin)
         karr = _ptr_array(kin) if nk else None
         aarr = (ctypes.c_double * nk)(*acoef) if nk else None
-        check(self.lib.gp_ode_rhs(ctypes.byref(self.h.w), ctypes.c_void_p(self.pobj.data_ptr()), t32, sig, coef,
-                                  ctypes.c_void_p(self.y.data_ptr()), karr, aarr, nk, float(h), self.R, self.k,
-                                  ctypes.c_void_p(kout.data_ptr()), ctypes.c_void_p(self.ws.data_ptr()),
-                                  self.ws.numel(), self._s()), "ode_rhs")
+        fn, head = self._entry("gp_ode_rhs")
+        check(fn(*head, ctypes.c_void_p(self.pobj.data_ptr()), t32, sig, coef,
+                 ctypes.c_void_p(self.y.data_ptr()), karr, aarr, nk, float(h), self.R, self.k,
+                 ctypes.c_void_p(kout.data_ptr()), ctypes.c_void_p(self.ws.data_ptr()),
+                 self.ws.numel(), self._s()), "ode_rhs")
+
+    def _device_stage_scalars(self, ts: List[float]):
+        """stage_scalars with the powers taken on the device: the control kernel's expressions (gp_ode.hip
+        ode_control_kernel: sigma = f32(sig_min) * f32(pow(base, f64(t32))), g = (sig_min * pow(base, t)) * scale),
+        every other operation IEEE float64 / float32 here as there. The energy backend's host-controlled attempts
+        take them, so that the host and the device controller run one arithmetic and give the same bits (a last-bit
+        difference of the host's pow from the device's otherwise sits in every K); the score backend keeps the
+        host scalars, which are the reference's."""
+        tt = np.asarray(ts, dtype=np.float64)
+        t32 = np.ascontiguousarray(tt.astype(np.float32))
+        ex = torch.from_numpy(np.concatenate([tt, t32.astype(np.float64)])).to(self.dev)
+        p = torch.pow(torch.full_like(ex, arch.SIGMA_MAX / arch.SIGMA_MIN), ex).cpu().numpy()
+        n = tt.shape[0]
+        sig = np.ascontiguousarray(np.float32(arch.SIGMA_MIN) * p[n:].astype(np.float32), dtype=np.float32)
+        g = (arch.SIGMA_MIN * p[:n]) * float(sde._DIFF_SCALE_T)
+        return t32, sig, np.ascontiguousarray(-(0.5 * (g * g)), dtype=np.float64)
+
+    def _device_err_pow(self, error_norm):
+        """error_norm ** -0.2 as the control kernel forms it (pow(err, -0.2) on the device)."""
+        e = torch.tensor([float(error_norm)], dtype=torch.float64, device=self.dev)
+        return np.float64(torch.pow(e, torch.full_like(e, ERROR_EXPONENT)).cpu().numpy()[0])
+
+    def _entry(self, name: str):
+        """(library entry, its leading weight arguments): `name`, or its energy form with the transposed weights."""
+        if self.energy_grad:
+            return getattr(self.lib, name + "_energy"), (ctypes.byref(self.h.w), ctypes.byref(self.h.grad_weights))
+        return getattr(self.lib, name), (ctypes.byref(self.h.w),)
 
     def set_t_eval(self, t_eval, direction, keep_all):
         self.t_eval = t_eval
@@ -349,10 +384,11 @@ class DeviceRk45:
 
     def attempt(self, t, h):
         stage_t = [t + c * h for c in C[1:]] + [t + h]   # rk_step: fun(t + c * h, ...) for s = 1..5, then t + h
-        t32, sig, coef = stage_scalars(stage_t)
+        t32, sig, coef = self._device_stage_scalars(stage_t) if self.energy_grad else stage_scalars(stage_t)
         self.y_new = torch.empty(self.n, dtype=torch.float64, device=self.dev)
-        check(self.lib.gp_ode_attempt(
-            ctypes.byref(self.h.w), ctypes.c_void_p(self.pobj.data_ptr()), t32.ctypes.data_as(ctypes.c_void_p),
+        fn, head = self._entry("gp_ode_attempt")
+        check(fn(
+            *head, ctypes.c_void_p(self.pobj.data_ptr()), t32.ctypes.data_as(ctypes.c_void_p),
             sig.ctypes.data_as(ctypes.c_void_p), coef.ctypes.data_as(ctypes.c_void_p),
             ctypes.c_void_p(self.y.data_ptr()), _ptr_array(self.K), _A6.ctypes.data_as(ctypes.c_void_p),
             _B6.ctypes.data_as(ctypes.c_void_p), _E7.ctypes.data_as(ctypes.c_void_p), float(h), self.rtol,
@@ -694,6 +730,7 @@ def rk45_device(be: DeviceRk45, t0: float, t_bound: float, t_eval: Optional[np.n
             ctypes.c_void_p(stream.cuda_stream))
 
     w, pobj = ctypes.byref(be.h.w), ctypes.c_void_p(be.pobj.data_ptr())
+    gw = ctypes.byref(be.h.grad_weights) if be.energy_grad else None
 
     def call(n, what, hp):
         if ex is not None:
@@ -702,6 +739,9 @@ def rk45_device(be: DeviceRk45, t0: float, t_bound: float, t_eval: Optional[np.n
             if ex.error is not None:
                 raise RuntimeError("ode_auto_attempt_global: partials exchange failed") from ex.error
             check(rc, "ode_auto_attempt_global")
+        elif be.energy_grad:   # host_status may be null there
+            check(lib.gp_ode_auto_attempt_energy(w, gw, pobj, n, what, *args[:-1], hp, args[-1]),
+                  "ode_auto_attempt_energy")
         elif hp is not None:
             check(lib.gp_ode_auto_attempt_hs(w, pobj, n, what, *args[:-1], hp, args[-1]), "ode_auto_attempt")
         else:

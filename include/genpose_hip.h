@@ -541,6 +541,46 @@ int gp_ode_denoise(const gp_head_weights *w, const float *pobj, float t32, float
                    float step, const double *x, int rows, int k, const float *pts_center,
                    double *pose, double *q, void *workspace, size_t workspace_bytes,
                    hipStream_t stream);
+/* The ODE sampler for the energy agent: cond_ode_sampler calls score_model(data) whichever agent it samples
+ * (samplers.py:204-219), and PoseEnergyNet answers with grad_x E, E = sum_o x_o f_o(x) / sigma
+ * (energynet.py:211-233). Each entry takes the arguments of its namesake plus gw, the transposed weights of the
+ * reverse pass (gp_head_grad_weights, as gp_energy_score_eval), and does what its namesake does with that score
+ * in place of f / (sigma + 1e-7): a stage's score equals gp_energy_score_eval on float(y_in) at the stage's time
+ * row and sigma bit for bit (plain sigma, which must be positive). Exact fp32 on 16-row tiles whatever
+ * arithmetic w selects. The stage combination, K = coef * double(score), y_new, the error terms and their fixed
+ * summation order, the controller, the dense output and the select_initial_step norms are the score path's own
+ * (gp_ode_init_norms, gp_ode_dense and the controller records serve both agents).
+ * Workspaces: the existing sizes suffice and are reused -- gp_ode_workspace_size(rows) for gp_ode_rhs_energy,
+ * gp_ode_attempt_energy and gp_ode_denoise_energy (one error partial per 16 rows is this tiling's count),
+ * gp_ode_auto_workspace_size(rows) for gp_ode_auto_attempt_energy, gp_ode_sample_workspace_size(rows) for
+ * gp_ode_sample_energy. gp_ode_auto_attempt_energy takes the host_status of gp_ode_auto_attempt_hs, which may
+ * be NULL here (no report to the host). Per-object and global-batch coupling have no energy form.
+ * Bad arguments (a NULL gw or gw plane included) return a status and set gp_last_error() before anything is
+ * launched. */
+int gp_ode_rhs_energy(const gp_head_weights *w, const gp_head_grad_weights *gw, const float *pobj,
+                      float t32, float sigma, double coef, const double *y, const double *const *kin,
+                      const double *acoef, int nk, double h, int rows, int k, double *kout,
+                      void *workspace, size_t workspace_bytes, hipStream_t stream);
+int gp_ode_attempt_energy(const gp_head_weights *w, const gp_head_grad_weights *gw, const float *pobj,
+                          const float *t32_6, const float *sigma_6, const double *coef_6,
+                          const double *y, double *const *kslots, const double *tableau_a,
+                          const double *b, const double *e, double h, double rtol, double atol, int rows,
+                          int k, double *ynew, double *err_out, void *workspace, size_t workspace_bytes,
+                          hipStream_t stream);
+int gp_ode_auto_attempt_energy(const gp_head_weights *w, const gp_head_grad_weights *gw, const float *pobj,
+                               int n, int what, double t_bound, double direction, double rtol,
+                               double atol, double sig_min, double base, double diff_scale, double *y0,
+                               double *y1, double *const *kslots, const double *tableau_a,
+                               const double *b, const double *e, int rows, int k, void *workspace,
+                               size_t workspace_bytes, int *host_status, hipStream_t stream);
+int gp_ode_denoise_energy(const gp_head_weights *w, const gp_head_grad_weights *gw, const float *pobj,
+                          float t32, float sigma, float g2, float step, const double *x, int rows, int k,
+                          const float *pts_center, double *pose, double *q, void *workspace,
+                          size_t workspace_bytes, hipStream_t stream);
+int gp_ode_sample_energy(const gp_head_weights *w, const gp_head_grad_weights *gw, const float *pobj,
+                         const float *x0, int rows, int k, double T0, double eps, int steps, double rtol,
+                         double atol, const float *pts_center, double *pose, double *q, int *nfev,
+                         int *status, void *workspace, size_t workspace_bytes, hipStream_t stream);
 
 /* ===================================================================== ImgEncoder (--dino pointwise)
  * ImgEncoder.forward (networks/img_encoder/img_encoder.py:48-100) over the three DINOv3 intermediate
