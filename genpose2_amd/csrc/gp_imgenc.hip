@@ -7,7 +7,7 @@
 //                     and the weighted sum -- a wave per token;
 //   edge branch       Conv2d(d, d/4, 3, padding 1) as an im2col GEMM (gp_linear with ReLU, the conv weight
 //                     (d/4, d*9) as stored: columns in [c][dy][dx] order) over object chunks, then the mean
-//                     over the 16 x 16 pixels in the reference's sequential order;
+//                     over the pixels (16 partial sums and a fixed tree);
 //   geo attention     S = G G^T (G = the last 3d/4 channels) and O = P F as batched exact-fp32 MFMA GEMMs,
 //                     S x (the host-built position table) and the row softmax between them, a wave per row;
 //   final mix         (F + relu(geo_w) O) + relu(edge_w) (F x edge[c % (d/4)]), in the reference's order.
@@ -100,25 +100,30 @@ __global__ void imgenc_nbr_max_kernel(const float* __restrict__ pmax, int t, int
     rmax[r] = v;
 }
 
-// edge[b][o] = (sum_p y[b][p][o], p in order) / np -- AdaptiveAvgPool2d(1)'s sequential sum (np = 256: the
-// division is exact scaling, as the reference's / kh / kw)
+// edge[b][o] = (sum_p y[b][p][o]) / np -- AdaptiveAvgPool2d(1). 16 partial sums (pixel p into sum p % 16) joined by
+// a fixed tree: one running fp32 sum of np non-negative terms drifts with sqrt(np) and chains np dependent adds.
+// The order depends on np alone, so an object's edge weights do not depend on the batch it is in.
 __global__ void imgenc_pool_kernel(const float* __restrict__ y, int nb, int np, int co, float* __restrict__ edge) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= nb * co) return;
     const int b = e / co, o = e - b * co;
     const float* yp = y + (size_t)b * np * co + o;
-    float s = 0.f;
+    float s[16];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) s[j] = 0.f;
     int p = 0;
-    // 16 loads in flight per step, added in p order (a load per dependent add waited ~600 cycles each)
-    for (; p + 16 <= np; p += 16) {
-        float v[16];
+    for (; p + 16 <= np; p += 16) {   // 16 loads in flight per step
 #pragma unroll
-        for (int j = 0; j < 16; ++j) v[j] = yp[(size_t)(p + j) * co];
-#pragma unroll
-        for (int j = 0; j < 16; ++j) s += v[j];
+        for (int j = 0; j < 16; ++j) s[j] += yp[(size_t)(p + j) * co];
     }
-    for (; p < np; ++p) s += yp[(size_t)p * co];
-    edge[e] = s / (float)np;
+#pragma unroll
+    for (int j = 0; j < 15; ++j)      // a tail (the encoder's np is a multiple of 16: none)
+        if (p + j < np) s[j] += yp[(size_t)(p + j) * co];
+#pragma unroll
+    for (int w = 8; w >= 1; w >>= 1)
+#pragma unroll
+        for (int j = 0; j < w; ++j) s[j] += s[j + w];
+    edge[e] = s[0] / (float)np;
 }
 
 // ---------------------------------------------------------------- batched GEMM (exact f32 MFMA)
