@@ -223,6 +223,12 @@ _SIGS: Dict[str, tuple] = {
                                  c_float, c_float, c_float, c_float, c_uint64, c_void_p, c_void_p, c_void_p,
                                  c_void_p, c_void_p, c_size_t, c_void_p]),
     "gp_frame_roi_rgb": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "gp_frames_mask_stats": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "gp_frames_objects": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                  c_int, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                  c_size_t, c_void_p]),
+    "gp_frames_roi_rgb": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p,
+                                  c_void_p]),
 }
 
 EXPORTED = tuple(_SIGS)

@@ -7,6 +7,10 @@
 //                             n_pts of them (tiling, or a keyed random selection), back-projection
 //   frame_roi_rgb_kernel      bilinear colour crop, uint8 rounding, ImageNet normalisation, CHW
 //
+// The gp_frames_* entries take F frames of one size stacked contiguously and the objects of all of them in one
+// launch: the statistics kernels carry the frame as a grid dimension, frames_objects_kernel and
+// frames_roi_rgb_kernel run the single-frame bodies on frame frame_of[b].
+//
 // Everything is integer or separately rounded fp32 / fp64 arithmetic with a fixed order, and the only atomics
 // are integer ones whose result does not depend on their order, so every output is bitwise reproducible.
 #include <limits.h>
@@ -24,10 +28,13 @@
 #define FR_WAVES (FR_THREADS / GP_WAVE)
 #define FR_MAX_PTS 2048
 #define FR_SAMPLE_TAG 0x53414D50u   // "SAMP": the sampling keys' Philox counter word 3
+#define FR_MAX_FRAMES 65535 // frames of one gp_frames_* call (a grid dimension of the statistics pass)
 
 // ============================================================================ mask statistics
+// blockIdx.x is the frame (one frame: a grid of 1)
 __global__ __launch_bounds__(FR_IDS) void frame_stats_init_kernel(int* __restrict__ stats, int h, int w) {
     const int id = threadIdx.x;
+    stats += (size_t)blockIdx.x * FR_IDS * FR_STAT;
     stats[id * FR_STAT + 0] = 0;
     stats[id * FR_STAT + 1] = h;
     stats[id * FR_STAT + 2] = -1;
@@ -49,6 +56,8 @@ __device__ __forceinline__ void stats_flush(int* s_tab, int id, int cnt, int r, 
 __global__ __launch_bounds__(256) void frame_mask_stats_kernel(const uint8_t* __restrict__ mask, int h, int w,
                                                                 int segs_per_row, int* __restrict__ stats) {
     __shared__ int s_tab[FR_IDS * FR_STAT];
+    mask += (size_t)blockIdx.y * h * w;   // blockIdx.y is the frame (one frame: gridDim.y = 1)
+    stats += (size_t)blockIdx.y * FR_IDS * FR_STAT;
     for (int id = threadIdx.x; id < FR_IDS; id += blockDim.x) {
         s_tab[id * FR_STAT + 0] = 0;
         s_tab[id * FR_STAT + 1] = h;
@@ -90,15 +99,27 @@ __global__ __launch_bounds__(256) void frame_mask_stats_kernel(const uint8_t* __
     }
 }
 
-extern "C" int gp_frame_mask_stats(const uint8_t* mask, int h, int w, int* stats, hipStream_t stream) {
-    GP_REQUIRE(mask && stats, "frame_mask_stats: null pointer");
-    GP_REQUIRE(h >= 1 && w >= 1 && (long long)h * w < INT_MAX, "frame_mask_stats: bad frame size %d x %d", h, w);
-    hipLaunchKernelGGL(frame_stats_init_kernel, dim3(1), dim3(FR_IDS), 0, stream, stats, h, w);
+// the init launch and the statistics launch over f frames
+static int launch_mask_stats(const uint8_t* mask, int f, int h, int w, int* stats, hipStream_t stream) {
+    hipLaunchKernelGGL(frame_stats_init_kernel, dim3(f), dim3(FR_IDS), 0, stream, stats, h, w);
     const int segs = (w + FR_SEG - 1) / FR_SEG;
     const long long nseg = (long long)h * segs;
     const int blocks = (int)std::min<long long>((nseg + 255) / 256, 256);
-    hipLaunchKernelGGL(frame_mask_stats_kernel, dim3(blocks), dim3(256), 0, stream, mask, h, w, segs, stats);
+    hipLaunchKernelGGL(frame_mask_stats_kernel, dim3(blocks, f), dim3(256), 0, stream, mask, h, w, segs, stats);
     return gp_check_launch("frame_mask_stats_kernel");
+}
+
+extern "C" int gp_frame_mask_stats(const uint8_t* mask, int h, int w, int* stats, hipStream_t stream) {
+    GP_REQUIRE(mask && stats, "frame_mask_stats: null pointer");
+    GP_REQUIRE(h >= 1 && w >= 1 && (long long)h * w < INT_MAX, "frame_mask_stats: bad frame size %d x %d", h, w);
+    return launch_mask_stats(mask, 1, h, w, stats, stream);
+}
+
+extern "C" int gp_frames_mask_stats(const uint8_t* mask, int f, int h, int w, int* stats, hipStream_t stream) {
+    GP_REQUIRE(mask && stats, "frames_mask_stats: null pointer");
+    GP_REQUIRE(f >= 1 && f <= FR_MAX_FRAMES, "frames_mask_stats: f=%d (1..%d)", f, FR_MAX_FRAMES);
+    GP_REQUIRE(h >= 1 && w >= 1 && (long long)h * w < INT_MAX, "frames_mask_stats: bad frame size %d x %d", h, w);
+    return launch_mask_stats(mask, f, h, w, stats, stream);
 }
 
 // ============================================================================ crop boxes (host)
@@ -158,7 +179,21 @@ __device__ __forceinline__ uint64_t sample_item(uint32_t e, uint32_t id, uint32_
     return ((uint64_t)r.x << 32) | e;
 }
 
-__global__ __launch_bounds__(FR_THREADS) void frame_objects_kernel(
+// Object b without a valid pixel (the caller raises on count < 10): defined outputs all the same.
+__device__ __forceinline__ void object_zero_outputs(int b, int n_pts, float* __restrict__ pts,
+                                                    int* __restrict__ roi_xs, int* __restrict__ roi_ys) {
+    float* opts = pts + (size_t)b * n_pts * 3;
+    int* oxs = roi_xs + (size_t)b * n_pts;
+    int* oys = roi_ys + (size_t)b * n_pts;
+    for (int j = threadIdx.x; j < n_pts; j += FR_THREADS) {
+        opts[3 * j] = opts[3 * j + 1] = opts[3 * j + 2] = 0.f;
+        oxs[j] = oys[j] = 0;
+    }
+}
+
+// Object b = blockIdx.x of the (h,w) frame at depth / mask, camera {fx, fy, cx, cy}, sampling key {k0, k1}: the
+// body of frame_objects_kernel (one frame) and frames_objects_kernel (the frame of frame_of[b]).
+__device__ __forceinline__ void frame_objects_body(
     const float* __restrict__ depth, const uint8_t* __restrict__ mask, int h, int w, const int* __restrict__ ids,
     const float* __restrict__ boxes, int s, int n_pts, int n_sort, float fx, float fy, float cx, float cy,
     float max_depth, uint32_t k0, uint32_t k1, uint32_t* __restrict__ vws, float* __restrict__ pts,
@@ -215,11 +250,8 @@ __global__ __launch_bounds__(FR_THREADS) void frame_objects_kernel(
     float* opts = pts + (size_t)b * n_pts * 3;
     int* oxs = roi_xs + (size_t)b * n_pts;
     int* oys = roi_ys + (size_t)b * n_pts;
-    if (c == 0) {   // nothing to sample (the caller raises on count < 10): defined outputs all the same
-        for (int j = tid; j < n_pts; j += FR_THREADS) {
-            opts[3 * j] = opts[3 * j + 1] = opts[3 * j + 2] = 0.f;
-            oxs[j] = oys[j] = 0;
-        }
+    if (c == 0) {   // nothing to sample
+        object_zero_outputs(b, n_pts, pts, roi_xs, roi_ys);
         return;
     }
     const bool select = c >= n_pts;
@@ -302,6 +334,36 @@ __global__ __launch_bounds__(FR_THREADS) void frame_objects_kernel(
     }
 }
 
+__global__ __launch_bounds__(FR_THREADS) void frame_objects_kernel(
+    const float* __restrict__ depth, const uint8_t* __restrict__ mask, int h, int w, const int* __restrict__ ids,
+    const float* __restrict__ boxes, int s, int n_pts, int n_sort, float fx, float fy, float cx, float cy,
+    float max_depth, uint32_t k0, uint32_t k1, uint32_t* __restrict__ vws, float* __restrict__ pts,
+    int* __restrict__ roi_xs, int* __restrict__ roi_ys, int* __restrict__ count) {
+    frame_objects_body(depth, mask, h, w, ids, boxes, s, n_pts, n_sort, fx, fy, cx, cy, max_depth, k0, k1, vws, pts,
+                       roi_xs, roi_ys, count);
+}
+
+// F stacked frames: object b reads frame frame_of[b], that frame's camera intr[4 f ..] and key seeds[2 f ..]. A
+// frame index outside [0, F) reads nothing: count 0 and zeroed outputs.
+__global__ __launch_bounds__(FR_THREADS) void frames_objects_kernel(
+    const float* __restrict__ depth, const uint8_t* __restrict__ mask, int nf, int h, int w,
+    const int* __restrict__ frame_of, const int* __restrict__ ids, const float* __restrict__ boxes, int s, int n_pts,
+    int n_sort, const float* __restrict__ intr, float max_depth, const uint32_t* __restrict__ seeds,
+    uint32_t* __restrict__ vws, float* __restrict__ pts, int* __restrict__ roi_xs, int* __restrict__ roi_ys,
+    int* __restrict__ count) {
+    const int b = blockIdx.x;
+    const int f = frame_of[b];
+    if (f < 0 || f >= nf) {   // the same for the whole workgroup
+        if (threadIdx.x == 0) count[b] = 0;
+        object_zero_outputs(b, n_pts, pts, roi_xs, roi_ys);
+        return;
+    }
+    const size_t off = (size_t)f * h * w;
+    frame_objects_body(depth + off, mask + off, h, w, ids, boxes, s, n_pts, n_sort, intr[4 * f + 0], intr[4 * f + 1],
+                       intr[4 * f + 2], intr[4 * f + 3], max_depth, seeds[2 * f + 0], seeds[2 * f + 1], vws, pts,
+                       roi_xs, roi_ys, count);
+}
+
 extern "C" size_t gp_frame_objects_workspace_size(int b, int img_size) {
     if (b <= 0 || img_size <= 0) return 0;
     return (size_t)b * img_size * img_size * sizeof(uint32_t);
@@ -336,12 +398,35 @@ extern "C" int gp_frame_objects(const float* depth, const uint8_t* mask, int h, 
     return gp_check_launch("frame_objects_kernel");
 }
 
+extern "C" int gp_frames_objects(const float* depth, const uint8_t* mask, int f, int h, int w, const int* frame_of,
+                                 const int* ids, const float* boxes, int b, int img_size, int n_pts,
+                                 const float* intr, float max_depth, const uint32_t* seeds, float* pts, int* roi_xs,
+                                 int* roi_ys, int* count, void* workspace, size_t workspace_bytes,
+                                 hipStream_t stream) {
+    GP_REQUIRE(f >= 1 && f <= FR_MAX_FRAMES, "frames_objects: f=%d (1..%d)", f, FR_MAX_FRAMES);
+    if (int rc = frame_check_common("frames_objects", h, w, b, img_size)) return rc;
+    GP_REQUIRE(b <= 65535, "frames_objects: b=%d exceeds 65535", b);
+    GP_REQUIRE(n_pts >= 1 && n_pts <= FR_MAX_PTS, "frames_objects: n_pts=%d (1..%d)", n_pts, FR_MAX_PTS);
+    GP_REQUIRE(pts && roi_xs && roi_ys && count, "frames_objects: null output");
+    if (b == 0) return GP_OK;
+    GP_REQUIRE(depth && mask && frame_of && ids && boxes && intr && seeds, "frames_objects: null input");
+    GP_REQUIRE(workspace && workspace_bytes >= gp_frame_objects_workspace_size(b, img_size),
+               "frames_objects: workspace of %zu bytes, %zu needed", workspace_bytes,
+               gp_frame_objects_workspace_size(b, img_size));
+    int n_sort = 2;
+    while (n_sort < n_pts) n_sort <<= 1;
+    hipLaunchKernelGGL(frames_objects_kernel, dim3(b), dim3(FR_THREADS), 0, stream, depth, mask, f, h, w, frame_of, ids,
+                       boxes, img_size, n_pts, n_sort, intr, max_depth, seeds, static_cast<uint32_t*>(workspace), pts,
+                       roi_xs, roi_ys, count);
+    return gp_check_launch("frames_objects_kernel");
+}
+
 // ============================================================================ colour crop
 // One thread per crop pixel: bilinear taps of the uint8 colour image at (u, v) (taps outside the image are 0),
 // rounded to a uint8 level as floor(value + 0.5), then (level / 255 - mean) / std, stored channel-major.
-__global__ __launch_bounds__(256) void frame_roi_rgb_kernel(const uint8_t* __restrict__ color, int h, int w,
-                                                             const float* __restrict__ boxes, int s,
-                                                             float* __restrict__ out) {
+// The body of frame_roi_rgb_kernel (one frame) and frames_roi_rgb_kernel (the frame of frame_of[b]).
+__device__ __forceinline__ void frame_roi_rgb_body(const uint8_t* __restrict__ color, int h, int w,
+                                                   const float* __restrict__ boxes, int s, float* __restrict__ out) {
 #pragma clang fp contract(off)
     const int b = blockIdx.y;
     const int npix = s * s;
@@ -373,6 +458,25 @@ __global__ __launch_bounds__(256) void frame_roi_rgb_kernel(const uint8_t* __res
     }
 }
 
+__global__ __launch_bounds__(256) void frame_roi_rgb_kernel(const uint8_t* __restrict__ color, int h, int w,
+                                                             const float* __restrict__ boxes, int s,
+                                                             float* __restrict__ out) {
+    frame_roi_rgb_body(color, h, w, boxes, s, out);
+}
+
+// A frame index outside [0, F) is an image of no pixels: every tap lies outside, nothing is read, level 0.
+__global__ __launch_bounds__(256) void frames_roi_rgb_kernel(const uint8_t* __restrict__ color, int nf, int h, int w,
+                                                              const int* __restrict__ frame_of,
+                                                              const float* __restrict__ boxes, int s,
+                                                              float* __restrict__ out) {
+    const int f = frame_of[blockIdx.y];
+    if (f < 0 || f >= nf) {
+        frame_roi_rgb_body(color, 0, 0, boxes, s, out);
+        return;
+    }
+    frame_roi_rgb_body(color + (size_t)f * h * w * 3, h, w, boxes, s, out);
+}
+
 extern "C" int gp_frame_roi_rgb(const uint8_t* color, int h, int w, const float* boxes, int b, int img_size,
                                 float* roi_rgb, hipStream_t stream) {
     if (int rc = frame_check_common("frame_roi_rgb", h, w, b, img_size)) return rc;
@@ -384,4 +488,18 @@ extern "C" int gp_frame_roi_rgb(const uint8_t* color, int h, int w, const float*
     hipLaunchKernelGGL(frame_roi_rgb_kernel, dim3((npix + 255) / 256, b), dim3(256), 0, stream, color, h, w, boxes,
                        img_size, roi_rgb);
     return gp_check_launch("frame_roi_rgb_kernel");
+}
+
+extern "C" int gp_frames_roi_rgb(const uint8_t* color, int f, int h, int w, const int* frame_of, const float* boxes,
+                                 int b, int img_size, float* roi_rgb, hipStream_t stream) {
+    GP_REQUIRE(f >= 1 && f <= FR_MAX_FRAMES, "frames_roi_rgb: f=%d (1..%d)", f, FR_MAX_FRAMES);
+    if (int rc = frame_check_common("frames_roi_rgb", h, w, b, img_size)) return rc;
+    GP_REQUIRE(b <= 65535, "frames_roi_rgb: b=%d exceeds 65535", b);
+    GP_REQUIRE(roi_rgb, "frames_roi_rgb: null output");
+    if (b == 0) return GP_OK;
+    GP_REQUIRE(color && frame_of && boxes, "frames_roi_rgb: null input");
+    const int npix = img_size * img_size;
+    hipLaunchKernelGGL(frames_roi_rgb_kernel, dim3((npix + 255) / 256, b), dim3(256), 0, stream, color, f, h, w,
+                       frame_of, boxes, img_size, roi_rgb);
+    return gp_check_launch("frames_roi_rgb_kernel");
 }

@@ -4,16 +4,18 @@
 and the ``EvaluationPipeline`` stages on its batch: score sampling (warm-started from ``prev_pose``), energy
 ranking with get_energy(T=None), aggregation, size. The reference calls ``get_objects()`` once per stage, so its
 EnergyNet and size stage see a fresh random sample of the points; here every stage reads the same sample.
+``GenPose2.inference_frames`` does the same for several frames in one call (frontend.frames_objects): one front
+end, one pipeline run on the objects of all frames, the results split by frame.
 """
 from __future__ import annotations
 
-from typing import Dict, Optional, Tuple, Union
+from typing import Dict, List, Optional, Sequence, Tuple, Union
 
 import torch
 
 from . import arch, device as dev
 from .config import GenPoseConfig
-from .frontend import InferDataset
+from .frontend import InferDataset, InferFrames
 from .runner import EvaluationPipeline
 
 
@@ -101,6 +103,45 @@ class GenPose2:
         final_pose = out.aggregated
         length = out.length if out.length is not None else dev.bbox_length(pts, final_pose)
         return final_pose, length
+
+    @torch.no_grad()
+    def inference_frames(self, data: Union[InferFrames, Dict[str, torch.Tensor]],
+                         prev_pose: Optional[Sequence[torch.Tensor]] = None, tracking: bool = False,
+                         tracking_T0: float = 0.15) -> List[Tuple[torch.Tensor, torch.Tensor]]:
+        """``inference`` for F frames in one call -> a list of F pairs (final_pose (B_f,4,4), final_length (B_f,3)),
+        each frame's objects in ascending mask id; a frame of background only gives empty tensors.
+
+        ``data``: an ``InferFrames`` (its ``get_objects()`` runs once) or a batch ``frames_objects`` returned. The
+        front end and ``pipeline.run`` run once on the B = sum B_f objects of all frames, and the results are split
+        by the batch's ``frame_offsets``. ``prev_pose``: ``None`` or a sequence of F tensors (B_f,4,4), a warm start
+        for every object (for none: ``None``); start time and crop-size check as in ``inference``.
+
+        It runs under ``self.cfg``. With ``ode_coupling="object"`` (or ``pc_coupling="object"`` for the PC sampler)
+        an object's candidates do not depend on which frames share the call; with the default ``"batch"`` coupling
+        they do, exactly as they already depend on the other objects of one frame (the step controller's error norm
+        and the Langevin step size are taken over the whole batch). Under either coupling an object's prior noise
+        is its rows of the whole call's draw: to reproduce a frame's objects in a call of their own, give the score
+        agent ``object_window = (B, frame_offsets[f])``."""
+        if self.cfg.dino == "pointwise" and hasattr(data, "get_objects") and hasattr(data, "_img_size"):
+            self.check_pointwise_size(data._img_size, data._img_size)   # before the front end launches anything
+        batch = data.get_objects() if hasattr(data, "get_objects") else data
+        if "frame_offsets" not in batch:
+            raise ValueError("inference_frames takes an InferFrames or a batch of frames_objects (with frame_offsets)")
+        offsets = [int(o) for o in batch["frame_offsets"]]
+        F = len(offsets) - 1
+        if prev_pose is not None:
+            prev_pose = list(prev_pose)
+            if len(prev_pose) != F:
+                raise ValueError(f"prev_pose holds {len(prev_pose)} tensors for {F} frames: one (B_f,4,4) per frame")
+            device = batch["pts"].device
+            prev_pose = [torch.as_tensor(p).to(device, torch.float32) for p in prev_pose]
+            for f, p in enumerate(prev_pose):
+                if tuple(p.shape) != (offsets[f + 1] - offsets[f], 4, 4):
+                    raise ValueError(f"prev_pose of frame {f} must be ({offsets[f + 1] - offsets[f]},4,4), "
+                                     f"got {tuple(p.shape)}")
+            prev_pose = torch.cat(prev_pose)
+        pose, length = self.inference(batch, prev_pose=prev_pose, tracking=tracking, tracking_T0=tracking_T0)
+        return [(pose[lo:hi], length[lo:hi]) for lo, hi in zip(offsets[:-1], offsets[1:])]
 
 
 def create_genpose2(score_model_path: Optional[str], energy_model_path: Optional[str] = None,

@@ -751,6 +751,30 @@ int gp_frame_objects(const float *depth, const uint8_t *mask, int h, int w, cons
 int gp_frame_roi_rgb(const uint8_t *color, int h, int w, const float *boxes, int b, int img_size, float *roi_rgb,
                      hipStream_t stream);
 
+/* ---- Several frames per call (DESIGN.md "Several frames per call"). f frames (1..65535) of one size, stacked
+ * contiguously on the device: depth (f,h,w) float32, mask (f,h,w) uint8, color (f,h,w,3) uint8. The objects of
+ * all frames form one batch of b (0..65535; 0 launches nothing), ordered by (frame, id), both ascending;
+ * frame_of (b) int32 on the device names each object's frame. Every output of an object has the bits the
+ * single-frame entries give on its frame alone. Call sequence: gp_frames_mask_stats, copy the f x 256 x 5
+ * statistics to the host, gp_frame_crop_boxes (host) once per frame on that frame's 256 x 5 slice, upload
+ * frame_of, ids and boxes, gp_frames_objects and gp_frames_roi_rgb, gp_points_mean; read `count`.
+ *
+ * stats (f,256,5) int32: gp_frame_mask_stats' table per frame, in one init and one statistics launch. */
+int gp_frames_mask_stats(const uint8_t *mask, int f, int h, int w, int *stats, hipStream_t stream);
+/* gp_frame_objects on frame frame_of[i] for object i, in one launch. intr (f,4) float32 {fx, fy, cx, cy} (already
+ * scaled; a zero focal length gives non-finite points) and seeds (f,2) uint32 {low, high half of the frame's
+ * 64-bit seed} are on the device, so cameras and seeds may differ per frame. The workspace is
+ * gp_frame_objects_workspace_size(b, img_size). An object whose frame_of lies outside [0, f) reads no frame: it
+ * gets count 0 and zeros. */
+int gp_frames_objects(const float *depth, const uint8_t *mask, int f, int h, int w, const int *frame_of,
+                      const int *ids, const float *boxes, int b, int img_size, int n_pts, const float *intr,
+                      float max_depth, const uint32_t *seeds, float *pts, int *roi_xs, int *roi_ys, int *count,
+                      void *workspace, size_t workspace_bytes, hipStream_t stream);
+/* gp_frame_roi_rgb on frame frame_of[i] for object i, in one launch (a frame_of outside [0, f): the crop of an
+ * image without pixels, level 0). */
+int gp_frames_roi_rgb(const uint8_t *color, int f, int h, int w, const int *frame_of, const float *boxes, int b,
+                      int img_size, float *roi_rgb, hipStream_t stream);
+
 /* ===================================================================== weight packing
  * The load path of PoseNet.load_ckpt -> load_state_dict (posenet_agent.py:171-203) for the --dino none
  * models, without Python: a model's state-dict tensors (HOST float32 arrays named by the reference's
