@@ -191,6 +191,14 @@ _SIGS: Dict[str, tuple] = {
     "gp_ode_sample_object": (c_int, [ctypes.POINTER(HeadWeights), c_void_p, c_void_p, c_int, c_int, c_int, c_double,
                                      c_double, c_int, c_double, c_double, c_void_p, c_void_p, c_void_p,
                                      ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_void_p, c_size_t, c_void_p]),
+    "gp_like_object_workspace_size": (c_size_t, [c_int]),
+    "gp_like_object_workspace_size_k": (c_size_t, [c_int, c_int]),
+    "gp_like_sample_object": (c_int, [ctypes.POINTER(HeadWeights), c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                      c_double, c_double, c_double, c_double, c_void_p, c_void_p,
+                                      ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_void_p, c_size_t, c_void_p]),
+    "gp_debug_like_obj_attempt": (c_int, [ctypes.POINTER(HeadWeights), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                          c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_double,
+                                          c_void_p]),
     "gp_img_encoder_workspace_size": (c_size_t, [c_int, c_int, c_int]),
     "gp_img_encoder": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_float,
                                c_void_p, c_void_p, c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p,

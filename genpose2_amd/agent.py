@@ -10,6 +10,7 @@ Every computation runs in libgenpose_hip.so; this class only moves tensors and s
 from __future__ import annotations
 
 import os
+import warnings
 from typing import Optional
 
 import numpy as np
@@ -57,7 +58,8 @@ class PoseNet:
         self.global_batch = None                   # shard.GlobalBatch: this call is one shard of a global-batch
                                                    # PC / ODE call (runner.ShardedEvaluationPipeline(global_batch=True))
         self.last_nfev_objects = self.last_status_objects = None   # ODE, cfg.ode_coupling == "object": per object
-        self.object_window = None                  # pc_coupling / ode_coupling == "object" (the sampler in use's):
+        self.object_window = None                  # pc_coupling / ode_coupling == "object" (the sampler in use's)
+                                                   # and get_likelihood under like_coupling == "object":
                                                    # (objects in the whole batch, index of this call's first
                                                    # object) when the call is a slice of a larger batch; None:
                                                    # the call is the whole batch
@@ -478,26 +480,60 @@ class PoseNet:
         pose_samples (bs,K,9): poses in the camera frame as pred_func returns them (pts_center is subtracted, as
         get_energy does). epsilon: the (bs*K,9) Hutchinson direction used as is; None draws the reference's
         prior((R,9)) = randn * sigma(T=1) (noise_feed.prior if set, else the agent's generator).
-        Returns (bs,K) float64, plus the latent z (bs,K,9) float64 with return_latent. Sets last_nfev."""
+        Returns (bs,K) float64, plus the latent z (bs,K,9) float64 with return_latent. Sets last_nfev.
+
+        cfg.like_coupling == "object": one solve per object over its own K poses (gp_like_sample_object: the
+        controller on the device, every norm over the object's 10 K entries), so an object's ll, latent, nfev and
+        status do not depend on the other objects of the call; last_nfev_objects / last_status_objects are set
+        (last_nfev is the maximum) and ``object_window = (total, first)`` makes the call objects
+        [first, first + bs) of a batch of ``total``: the drawn epsilon is those rows of the whole batch's draw, the
+        tile class that of total * K rows. pc_coupling / ode_coupling are not consulted."""
         if self.cfg.agent_type != "score":
             raise NotImplementedError("get_likelihood needs agent_type='score'")
+        like_object = self.cfg.like_coupling == "object"
         if self.global_batch is not None:
+            if like_object:
+                raise NotImplementedError("like_coupling='object' is not built for global-batch calls (per-object "
+                                          "solves need no exchange: set object_window instead)")
             raise NotImplementedError("get_likelihood has no global-batch mode")
-        if self.cfg.sampler_mode[0] == "ode" and self.cfg.ode_coupling == "object":
+        if not like_object and self.cfg.sampler_mode[0] == "ode" and self.cfg.ode_coupling == "object":
             raise NotImplementedError("ode_coupling='object' is not built for get_likelihood (its solve stays "
-                                      "batch-coupled: one step controller over every pose of the call)")
-        self.is_testing = True
+                                      "batch-coupled: one step controller over every pose of the call; "
+                                      "like_coupling='object' gives the likelihood one solve per object)")
         bs, K = pose_samples.shape[0], pose_samples.shape[1]
         R = bs * K
+        rows_total, row_off = R, 0
+        if self.object_window is not None:
+            if not like_object:
+                raise ValueError("object_window in get_likelihood belongs to like_coupling='object'")
+            total, first = (int(v) for v in self.object_window)
+            if not 0 <= first <= total - bs:
+                raise ValueError(f"object_window: objects [{first}, {first + bs}) outside a batch of {total}")
+            rows_total, row_off = total * K, first * K
+        self.is_testing = True
         feat = self._encode(data) if extract_feature else dev.require_device_tensor(data["pts_feat"], "pts_feat")
         data["pts_feat"] = feat
         pobj = self.heads.object_proj(feat)
         pose = pose_samples.to(self.device).reshape(R, -1).to(torch.float32).clone()
         center = dev.require_device_tensor(data["pts_center"], "pts_center")
         pose[:, -3:] -= center.unsqueeze(1).repeat(1, K, 1).view(R, -1)
-        if epsilon is None:
-            epsilon = self._draw_prior(R) * sde.prior_sigma(arch.SDE_T)
+        if epsilon is None:   # a window's rows are its rows of the whole batch's draw, as the samplers'
+            epsilon = self._draw_prior(rows_total)[row_off:row_off + R] * sde.prior_sigma(arch.SDE_T)
         eps_dir = epsilon.to(self.device, torch.float32).reshape(R, arch.POSE_DIM).contiguous()
+        if like_object:
+            # one RK45 solve per object (gp_like_sample_object): initial step, controller, latent and ll in the
+            # one call; an object whose solve fails (status -1) keeps its last state, as the reference's does
+            z, ll, nfev, status = self.heads.like_sample_object(pobj, pose, eps_dir, K, arch.SAMPLING_EPS, 1.0,
+                                                                rows_total=rows_total, rtol=rtol, atol=atol)
+            if (status < 0).any():
+                warnings.warn("RK45: required step size is less than spacing between numbers.")
+            self.last_nfev_objects, self.last_status_objects = nfev, status
+            self.last_nfev = int(nfev.max())
+            self._calls += 1
+            ll = ll.view(bs, K)
+            if return_latent:
+                return ll, z.view(bs, K, arch.POSE_DIM)
+            return ll
         be = LikelihoodRk45(self.heads, pobj, pose, eps_dir, K, rtol=rtol, atol=atol)
         # solve_ivp(ode_func, (eps, 1.0), init_inp) without t_eval; a failed solve (status -1) still hands
         # res.y[:, -1] on (samplers.py:97-100): rk45_drive warns and keeps the last state

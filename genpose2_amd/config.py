@@ -53,6 +53,11 @@ class GenPoseConfig:
     # takes its error norms over: batch (one solve_ivp on every row of the call, as the reference's evaluation
     # calls cond_ode_sampler) | object (one solve per object: its own steps, accept / reject and nfev)
     ode_coupling: str = "batch"
+    # the same choice for get_likelihood, whichever sampler the agent runs: batch (one solve_ivp over every pose of
+    # the call, as the reference's cond_ode_likelihood) | object (one solve per object over its own poses: its ll,
+    # latent, nfev and status do not depend on which other objects share the call). pc_coupling / ode_coupling are
+    # not consulted
+    like_coupling: str = "batch"
     # agent_type "energy" with the ODE sampler: the energy's gradient as the probability-flow ODE's score, as the
     # reference's cond_ode_sampler runs either agent (read only then). Off by default: the gradient is
     # discontinuous at ReLU kinks, so RK45 takes more evaluations than with the ScoreNet and is accurate to about
@@ -87,5 +92,7 @@ class GenPoseConfig:
             raise ValueError(f"pc_coupling {self.pc_coupling!r} (batch | object)")
         if self.ode_coupling not in ("batch", "object"):
             raise ValueError(f"ode_coupling {self.ode_coupling!r} (batch | object)")
+        if self.like_coupling not in ("batch", "object"):
+            raise ValueError(f"like_coupling {self.like_coupling!r} (batch | object)")
         if not isinstance(self.energy_ode, bool):
             raise ValueError(f"energy_ode {self.energy_ode!r} (True | False)")

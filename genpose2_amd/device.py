@@ -225,6 +225,7 @@ class HeadModel:
         self.set_arith(os.environ.get("GENPOSE2_HEAD_ARITH", "f16x3"))
         self._pc_ws: Optional[torch.Tensor] = None
         self._ode_obj_ws: Optional[torch.Tensor] = None
+        self._like_obj_ws: Optional[torch.Tensor] = None
         self._gw = None                                    # (buffers, HeadGradWeights)
 
     def weights_changed(self) -> None:
@@ -463,6 +464,35 @@ class HeadModel:
             status.ctypes.data_as(pi), ctypes.c_void_p(self._ode_obj_ws.data_ptr()), self._ode_obj_ws.numel(),
             self._s()), "ode_sample_object")
         return pose, q, nfev, status
+
+    def like_sample_object(self, pobj, x: torch.Tensor, eps_dir: torch.Tensor, k: int, t0: float, t_bound: float,
+                           rows_total=None, rtol: float = 1e-5, atol: float = 1e-5):
+        """cond_ode_likelihood with one RK45 solve per object (gp_like_sample_object): x (R,9) fp32, the poses the
+        model sees, and eps_dir (R,9) fp32, the Hutchinson direction -> z (R,9) and ll (R) fp64 on the device, and per
+        object nfev and status (NumPy int32, R // k). The call's rows may be a slice of a batch of ``rows_total``
+        rows (default R), which picks the tile class."""
+        R = x.shape[0]
+        rows_total = R if rows_total is None else int(rows_total)
+        x = require_device_tensor(x.to(self.device, torch.float32).contiguous(), "x")
+        eps_dir = require_device_tensor(eps_dir.to(self.device, torch.float32).contiguous(), "eps_dir")
+        if tuple(eps_dir.shape) != (R, arch.POSE_DIM):
+            raise ValueError(f"epsilon must be ({R}, {arch.POSE_DIM}), got {tuple(eps_dir.shape)}")
+        need = int(self.lib.gp_like_object_workspace_size_k(R, k)) if k >= 1 and R % k == 0 else 0
+        if self._like_obj_ws is None or self._like_obj_ws.numel() < need:
+            self._like_obj_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        z = torch.empty((R, arch.POSE_DIM), dtype=torch.float64, device=self.device)
+        ll = torch.empty((R,), dtype=torch.float64, device=self.device)
+        nobj = max(R // max(k, 1), 1)
+        nfev = np.zeros(nobj, np.int32)
+        status = np.zeros(nobj, np.int32)
+        pi = ctypes.POINTER(ctypes.c_int)
+        check(self.lib.gp_like_sample_object(
+            ctypes.byref(self.w), ctypes.c_void_p(pobj.data_ptr()), ctypes.c_void_p(x.data_ptr()),
+            ctypes.c_void_p(eps_dir.data_ptr()), R, k, rows_total, float(t0), float(t_bound), float(rtol), float(atol),
+            ctypes.c_void_p(z.data_ptr()), ctypes.c_void_p(ll.data_ptr()), nfev.ctypes.data_as(pi),
+            status.ctypes.data_as(pi), ctypes.c_void_p(self._like_obj_ws.data_ptr()), self._like_obj_ws.numel(),
+            self._s()), "like_sample_object")
+        return z, ll, nfev, status
 
     def ode_sample_energy(self, pobj, x0: torch.Tensor, k: int, pts_center: torch.Tensor, T0: float, eps: float,
                           steps: Optional[int], rtol: float = 1e-5, atol: float = 1e-5):

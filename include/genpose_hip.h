@@ -296,6 +296,17 @@ int gp_debug_ode_obj_control(const gp_head_weights *w, const float *pobj, const 
                              int nobj, float *init, unsigned long long *count, int *host_status, int *dev_status,
                              hipStream_t stream);
 
+/* Test aid for the per-object likelihood (gp_like_sample_object): one launch of its attempt kernel (the six RK45
+ * stages of every active object) as the entry launches it, from host-given records on caller-owned DEVICE buffers.
+ * rec: rows / k controller records (gp_debug_ode_obj_control's layout); h, t32[6], sig[6], coef[6], active and pend
+ * are read. y, ynew and the seven K slots (kslots: HOST array of device pointers; K_0 given) are 10 rows doubles
+ * each, [x (9 rows) | logp (rows)]; rowsq (rows) receives, per row of an active object, the sum over its ten entries
+ * of (err/scale)^2 in entry order. scratch: (6 rows / k + 1) * 768 floats. An inactive object's rows are not
+ * written. Not part of the likelihood's contract: the entry does not call it. */
+int gp_debug_like_obj_attempt(const gp_head_weights *w, const float *pobj, const void *rec, const float *eps_dir,
+                              double *y, double *ynew, double *const *kslots, double *rowsq, float *scratch,
+                              int rows, int k, int rows_total, double rtol, double atol, hipStream_t stream);
+
 /* ===================================================================== PC sampler
  * cond_pc_sampler (samplers.py:113-177) for R = b*k rows over T steps, fused per step:
  * [finish step i-1: Langevin corrector with the batch-mean score norm, renormalise,
@@ -432,6 +443,36 @@ int gp_like_attempt(const gp_head_weights *w, const float *pobj, const float *t3
                     double *const *kslots, const double *tableau_a, const double *b, const double *e,
                     double h, double rtol, double atol, int rows, int k, double *ynew,
                     double *err_out, void *workspace, size_t workspace_bytes, hipStream_t stream);
+/* Per-object likelihood: cond_ode_likelihood as the reference runs it when called once per object on that
+ * object's k poses. Every object has its own solve_ivp(RK45) over [x_b (9 k) | logp_b (k)] from t0 to t_bound: its
+ * own select_initial_step, step controller, stage times, accept / reject and nfev, and RMS norms over its own 10 k
+ * entries (the host-controlled solve over gp_like_attempt takes them over every row of the call). A norm's sum is
+ * taken per row over its ten entries in entry order (nine x, then logp), then over the object's rows j < k in an
+ * order that is a function of j and k alone (gp_ode_sample_object's). x (rows,9) fp32: the poses the model sees
+ * (pts_center subtracted); eps_dir (rows,9) fp32: the Skilling-Hutchinson direction, constant over the solve. rows
+ * (whole objects: a multiple of k) are a slice of a batch of rows_total rows (whole objects, >= rows): rows_total
+ * selects the tile class (one primal and one tangent tile per workgroup; two pairs from 4,097 rows with the f16x3
+ * trunk). pobj, x, eps_dir and the outputs hold this call's objects and rows only.
+ * DEVICE outs: z (rows,9) fp64, the latent res.y[:9 k, -1] of every object, and ll (rows) fp64,
+ * (prior_logp(z) + delta_logp) / ln 2 with the reference's float32 sigma_max and log term (samplers.py:14-22,
+ * 100-109). HOST outs, one per object (rows / k): nfev (2 + 6 attempts), status (1 done, -1 step size below the
+ * spacing of t: the object keeps its last state, as the reference does, and the others go on). A finished or
+ * failed object is not written again while the others go on; the call runs as many attempts as its slowest object.
+ * Contract: an object's ll, z, nfev and status are bit-identical for any set of other objects in the call and for
+ * any split of a batch into calls, given the same rows_total, x and eps_dir rows, weights and arithmetic, t0,
+ * t_bound, rtol and atol. No exchange between ranks.
+ * Workspace: gp_like_object_workspace_size_k(rows, k) bytes (0 when rows are not whole objects);
+ * gp_like_object_workspace_size(rows) is enough for every k. Status reads, their 60 s poll limit, the
+ * GENPOSE2_ODE_ZC=0 event-and-copy form and the limit of 100,000 attempts are gp_ode_sample_object's: a stuck
+ * solve returns an error. Bad arguments (rows that are not whole objects, a rows_total smaller than the call or not
+ * whole objects, t0 == t_bound, a workspace that is too small, a null pointer) return a status and set
+ * gp_last_error() before anything is launched. */
+size_t gp_like_object_workspace_size(int rows);
+size_t gp_like_object_workspace_size_k(int rows, int k);
+int gp_like_sample_object(const gp_head_weights *w, const float *pobj, const float *x, const float *eps_dir,
+                          int rows, int k, int rows_total, double t0, double t_bound, double rtol, double atol,
+                          double *z, double *ll, int *nfev, int *status, void *workspace,
+                          size_t workspace_bytes, hipStream_t stream);
 /* Dense output of an accepted step (scipy RkDenseOutput): for i in [i0, i1),
  * x = (t_eval[i] - t_old)/h, out[row] = h * (K^T P) cumprod([x,x,x,x]) + y_old with
  * row = reverse ? i_base - i : i - i_base. P7x4 (HOST 7x4), kslots (HOST, 7 device pointers). */
