@@ -4,18 +4,16 @@
 // reject and nfev, its RMS norms over its own 10 k entries, so its result does not depend on which other objects
 // share the call.
 //
-// The per-object machinery is gp_ode_sample_object's (gp_ode.hip): one OdeObjRec per object, decided and prepared
-// by ode_obj_control_kernel (unchanged: the norm's count is 10 k here, the direction +1), the folded rows
+// The per-object machinery is gp_ode_sample_object's, and the solve itself is the same host driver (ode_obj_solve,
+// gp_ode.hip) with this file's stage launch: one OdeObjRec per object, decided and prepared by
+// ode_obj_control_kernel (the norm's count is 10 k here, the direction +1), the folded rows
 // init[s][b] = pobj[b] + tproj(t32[b][s]) and the row of -0.0f in place of the trunk's pobj and tproj, the status
 // words and their poll. What differs is the stage: like_obj_attempt_kernel carries the JVP trunk of
 // like_stage_kernel (NP primal column tiles and their NP tangent tiles; the tangent columns see no pobj / tproj
 // term), the state is scipy's flat [x (9 R) | logp (R)] of the call's R rows, and a row's error sum covers its ten
 // entries in entry order (nine x, then logp). These kernels have a translation unit of their own so that they
 // cannot move the register assignment of the kernels that were there before them.
-#include <chrono>
 #include <cstddef>
-#include <cstdlib>
-#include <vector>
 
 #include "gp_ode.h"
 
@@ -179,42 +177,6 @@ __global__ __launch_bounds__(EVAL_WV * 64) void like_obj_attempt_kernel(LikeObjA
     }
 }
 
-// select_initial_step norms of every object (scipy _ivp/common.py) over its 10 k entries, one wave per object:
-// ode_obj_init_norms_kernel with a row's ten entries (nine x, then logp) in entry order, the rows by
-// ode_obj_wave_sum. f1 == NULL: out[3 b] = rms(y0 / scale), out[3 b + 1] = rms(f0 / scale); else
-// out[3 b + 2] = rms((f1 - f0) / scale); scale = atol + |y0| rtol.
-__global__ __launch_bounds__(64) void like_obj_init_norms_kernel(const double* __restrict__ y0,
-                                                                 const double* __restrict__ f0,
-                                                                 const double* __restrict__ f1, int rows, int kper,
-                                                                 double atol, double rtol, double* __restrict__ out) {
-#pragma clang fp contract(off)
-    const int b = blockIdx.x;
-    const size_t n9 = (size_t)rows * 9;
-    auto row = [&](int j, int which) {
-        const size_t r = (size_t)b * kper + j;
-        double sq = 0.0;
-        for (int o = 0; o < 10; ++o) {
-            const size_t e = o < 9 ? r * 9 + o : n9 + r;
-            const double sc = atol + fabs(y0[e]) * rtol;
-            const double v = which == 0 ? y0[e] / sc : (which == 1 ? f0[e] / sc : (f1[e] - f0[e]) / sc);
-            sq = o == 0 ? v * v : sq + v * v;
-        }
-        return sq;
-    };
-    const double rn = sqrt((double)kper * 10.0);
-    if (f1 == nullptr) {
-        const double s0 = ode_obj_wave_sum(kper, [&](int j) { return row(j, 0); });
-        const double s1 = ode_obj_wave_sum(kper, [&](int j) { return row(j, 1); });
-        if (threadIdx.x == 0) {
-            out[3 * b] = sqrt(s0) / rn;
-            out[3 * b + 1] = sqrt(s1) / rn;
-        }
-    } else {
-        const double s2 = ode_obj_wave_sum(kper, [&](int j) { return row(j, 2); });
-        if (threadIdx.x == 0) out[3 * b + 2] = sqrt(s2) / rn;
-    }
-}
-
 // y = [float64(x) (9 R) | init_logp = 0 (R)] (samplers.py:92)
 __global__ __launch_bounds__(256) void like_obj_state_kernel(const float* __restrict__ x, double* __restrict__ y,
                                                              long long n9, long long n) {
@@ -254,25 +216,19 @@ __global__ __launch_bounds__(256) void like_obj_final_kernel(LikeObjFinalArgs a)
 
 namespace {
 struct LikeObjLayout {
-    size_t y, ynew, k[ODE_NK], f1, dlogp, rowsq, norms, rec, init, zrow, count, dstat, total;
+    size_t y, ynew, k[ODE_NK], f1, dlogp, total;
+    OdeObjTail tail;
 };
 LikeObjLayout like_obj_layout(int rows, int nobj) {
     LikeObjLayout L = {};
     const size_t vec = align256((size_t)rows * 10 * sizeof(double));
-    const size_t rowv = align256((size_t)rows * sizeof(double));
     size_t off = 0;
     L.y = off; off += vec;
     L.ynew = off; off += vec;
     for (int j = 0; j < ODE_NK; ++j) { L.k[j] = off; off += vec; }
     L.f1 = off; off += vec;
-    L.dlogp = off; off += rowv;
-    L.rowsq = off; off += rowv;
-    L.norms = off; off += align256((size_t)nobj * 3 * sizeof(double));
-    L.rec = off; off += align256((size_t)nobj * 2 * sizeof(OdeObjRec));
-    L.init = off; off += align256((size_t)nobj * 6 * 768 * sizeof(float));
-    L.zrow = off; off += align256(768 * sizeof(float));
-    L.count = off; off += 256;
-    L.dstat = off; off += 256;
+    L.dlogp = off; off += align256((size_t)rows * sizeof(double));
+    L.tail = ode_obj_tail_layout(off, rows, nobj);
     L.total = off;
     return L;
 }
@@ -280,6 +236,31 @@ LikeObjLayout like_obj_layout(int rows, int nobj) {
 // Primal column tiles per workgroup: like_stage_kernel's rule (gp_ode.hip like_np) on the whole batch's rows
 int like_obj_np(const gp_head_weights* w, int rows_total) {
     return (w->pe2_h != nullptr && rows_total >= PC_SPLIT_NT2_MIN) ? 2 : 1;
+}
+
+// The stage arguments but for the records and `single` (f1: null where only attempts run)
+LikeObjArgs like_obj_args(const gp_head_weights* w, const float* init, const float* zrow, const float* eps, double* y,
+                          double* ynew, double* const* kslots, double* f1, double* rowsq, double rtol, double atol,
+                          int rows, int k) {
+    LikeObjArgs a = {};
+    a.w = *w;
+    a.init = init;
+    a.zrow = zrow;
+    a.eps = eps;
+    a.y = y;
+    a.ynew = ynew;
+    for (int j = 0; j < ODE_NK; ++j) {
+        a.k[j] = kslots[j];
+        a.e[j] = kE7[j];
+    }
+    a.f1 = f1;
+    a.rowsq = rowsq;
+    a.rtol = rtol;
+    a.atol = atol;
+    a.rows = rows;
+    a.kper = k;
+    a.nobj = rows / k;
+    return a;
 }
 
 int like_obj_launch(const LikeObjArgs& a, const OdeTableau& tb, int np, hipStream_t stream) {
@@ -313,184 +294,32 @@ extern "C" int gp_like_sample_object(const gp_head_weights* w, const float* pobj
     const LikeObjLayout L = like_obj_layout(rows, nobj);
     GP_REQUIRE(workspace_bytes >= L.total,
                "like_sample_object: workspace too small (gp_like_object_workspace_size_k(rows, k))");
-    StatusLease status;
-    GP_REQUIRE(status.acquire(stream) == 0, "like_sample_object: pinned status word / event");
     char* ws = static_cast<char*>(workspace);
     auto dptr = [&](size_t off) { return reinterpret_cast<double*>(ws + off); };
-    OdeObjRec* rec = reinterpret_cast<OdeObjRec*>(ws + L.rec);   // rec[parity * nobj + b]
-    float* init = reinterpret_cast<float*>(ws + L.init);
-    float* zrow = reinterpret_cast<float*>(ws + L.zrow);
-    unsigned long long* count = reinterpret_cast<unsigned long long*>(ws + L.count);
-    int* dstat = reinterpret_cast<int*>(ws + L.dstat);
-    double* norms = dptr(L.norms);
+    const OdeObjSolve sv(w, pobj, nobj, k, 10, t0, t_bound, rtol, atol, ws, L.tail, stream, "like_sample_object");
     const long long n9 = (long long)rows * 9, n = (long long)rows * 10;
-    const double tf = t_bound, dir = tf > t0 ? 1.0 : -1.0;
-    const double dscale = diff_scale();
     const int np = like_obj_np(w, rows_total);   // the whole batch's tile class
-    // every norm of an object runs over its 10 k entries
-    const OdeConsts kc = {tf, dir, rtol, atol, kSigMin, kBase, dscale, (double)k * 10.0, 0};
-
-    LikeObjArgs a = {};
-    a.w = *w;
-    a.init = init;
-    a.zrow = zrow;
-    a.eps = eps_dir;
-    a.y = dptr(L.y);
-    a.ynew = dptr(L.ynew);
-    for (int j = 0; j < ODE_NK; ++j) {
-        a.k[j] = dptr(L.k[j]);
-        a.e[j] = kE7[j];
-    }
-    a.f1 = dptr(L.f1);
-    a.rowsq = dptr(L.rowsq);
-    a.rtol = rtol;
-    a.atol = atol;
-    a.rows = rows;
-    a.kper = k;
-    a.nobj = nobj;
-    OdeTableau tb;
-    for (int j = 0; j < 36; ++j) tb.A[j] = kA6[j];
-    for (int j = 0; j < 6; ++j) tb.B[j] = kB6[j];
+    double* K[ODE_NK];
+    for (int j = 0; j < ODE_NK; ++j) K[j] = dptr(L.k[j]);
+    LikeObjArgs a = like_obj_args(w, sv.init, sv.zrow, eps_dir, dptr(L.y), dptr(L.ynew), K, dptr(L.f1), sv.rowsq, rtol,
+                                  atol, rows, k);
+    const OdeTableau tb = ode_tableau();
     auto stages = [&](const OdeObjRec* r, int single) {
         a.rec = r;
         a.single = single;
         return like_obj_launch(a, tb, np, stream);
     };
-    // rows of slot 0 for host-prepared records (the two select_initial_step evaluations)
-    auto rows0 = [&](const OdeObjRec* r) {
-        return ode_obj_launch_control(w, pobj, r, nullptr, nullptr, 0, 0, 1, kc, k, nobj, init, count, nullptr, dstat, 0,
-                                      stream);
+    auto init_norms = [&](bool with_f1) {
+        hipLaunchKernelGGL(ode_obj_init_norms_kernel<10>, dim3(nobj), dim3(64), 0, stream, (const double*)a.y,
+                           (const double*)a.k[0], (const double*)(with_f1 ? a.f1 : nullptr), rows, k, atol, rtol,
+                           sv.norms);
+        return gp_check_launch("ode_obj_init_norms_kernel");
     };
     int rc;
-    GP_REQUIRE(hipMemsetAsync(count, 0, 256, stream) == hipSuccess, "like_sample_object: counter");
-    if ((rc = ode_obj_launch_fill(zrow, 768, -0.0f, stream))) return rc;
     hipLaunchKernelGGL(like_obj_state_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, x, a.y, n9, n);
     if ((rc = gp_check_launch("like_obj_state_kernel"))) return rc;
-
-    // ---- select_initial_step (scipy common.py) per object, gp_ode_sample_object's scalar expressions element by
-    //      element
-    std::vector<OdeObjRec> hrec((size_t)nobj);
-    std::vector<double> hn((size_t)nobj * 3);
-    auto upload = [&](int parity) {
-        return hipMemcpyAsync(rec + (size_t)parity * nobj, hrec.data(), sizeof(OdeObjRec) * (size_t)nobj,
-                              hipMemcpyHostToDevice, stream) == hipSuccess &&
-               hipStreamSynchronize(stream) == hipSuccess;
-    };
-    auto norms_back = [&]() {
-        return hipMemcpyAsync(hn.data(), norms, sizeof(double) * 3 * (size_t)nobj, hipMemcpyDeviceToHost, stream) ==
-                   hipSuccess && hipStreamSynchronize(stream) == hipSuccess;
-    };
-    auto init_norms = [&](const double* f1) {
-        hipLaunchKernelGGL(like_obj_init_norms_kernel, dim3(nobj), dim3(64), 0, stream, (const double*)a.y,
-                           (const double*)a.k[0], f1, rows, k, atol, rtol, norms);
-        return gp_check_launch("like_obj_init_norms_kernel");
-    };
-    {   // f(t0): solve_ivp hands t0 as a Python float, so ode_func's g is float32 sigma * float64 scale
-        const float t32 = (float)t0;
-        const double g = (double)sigma32(t32) * dscale;
-        for (int b = 0; b < nobj; ++b) {
-            OdeObjRec r = {};
-            r.t = t0;
-            r.active = 1;
-            r.t32[0] = t32;
-            r.sig[0] = sigma32(t32);
-            r.coef[0] = -(0.5 * (g * g));
-            hrec[(size_t)b] = r;
-        }
-    }
-    GP_REQUIRE(upload(0), "like_sample_object: records");
-    if ((rc = rows0(rec))) return rc;
-    if ((rc = stages(rec, 1))) return rc;
-    if ((rc = init_norms(nullptr))) return rc;
-    GP_REQUIRE(norms_back(), "like_sample_object: norm read");
-    const double interval = fabs(tf - t0);
-    std::vector<double> h0v((size_t)nobj);
-    for (int b = 0; b < nobj; ++b) {
-        const double d0 = hn[3 * (size_t)b], d1 = hn[3 * (size_t)b + 1];
-        double h0 = (d0 < 1e-5 || d1 < 1e-5) ? 1e-6 : 0.01 * d0 / d1;
-        h0 = fmin(h0, interval);
-        h0v[(size_t)b] = h0;
-        // f(t0 + h0 dir, y0 + h0 dir f0): a NumPy float64 time from here on
-        const double t = t0 + h0 * dir;
-        const double g = kSigMin * pow(kBase, t) * dscale;
-        OdeObjRec& r = hrec[(size_t)b];
-        r.h = h0 * dir;
-        r.t32[0] = (float)t;
-        r.sig[0] = sigma32((float)t);
-        r.coef[0] = -(0.5 * (g * g));
-    }
-    GP_REQUIRE(upload(1), "like_sample_object: records");
-    if ((rc = rows0(rec + nobj))) return rc;
-    if ((rc = stages(rec + nobj, 2))) return rc;
-    if ((rc = init_norms(a.f1))) return rc;
-    GP_REQUIRE(norms_back(), "like_sample_object: norm read");
-    for (int b = 0; b < nobj; ++b) {
-        const double d1 = hn[3 * (size_t)b + 1], h0 = h0v[(size_t)b];
-        const double d2 = hn[3 * (size_t)b + 2] / h0;
-        const double h1 = (d1 <= 1e-15 && d2 <= 1e-15) ? fmax(1e-6, h0 * 1e-3) : pow(0.01 / fmax(d1, d2), 1.0 / 5.0);
-        OdeObjRec r = {};
-        r.t = t0;
-        r.h_abs = fmin(fmin(100 * h0, h1), interval);
-        r.nfev = 2;
-        hrec[(size_t)b] = r;
-    }
-    GP_REQUIRE(upload(0), "like_sample_object: records");
-
-    // ---- the attempts, one enqueued ahead of the status read; the loop ends when no object runs
-    int* hs_dev = nullptr;   // the pinned words as the device addresses them, if it can
-    {
-        const char* zc = getenv("GENPOSE2_ODE_ZC");
-        if ((zc != nullptr && zc[0] == '0') ||
-            hipHostGetDevicePointer(reinterpret_cast<void**>(&hs_dev), status.r.pinned, 0) != hipSuccess) {
-            hs_dev = nullptr;
-            (void)hipGetLastError();
-        }
-    }
-    auto control = [&](int at) {   // decides attempt at - 1, prepares attempt at
-        return ode_obj_launch_control(w, pobj, rec + (size_t)(at & 1) * nobj, rec + (size_t)((at + 1) & 1) * nobj,
-                                      a.rowsq, at > 0 ? 1 : 0, 1, 6, kc, k, nobj, init, count, hs_dev, dstat, at, stream);
-    };
-    auto attempt = [&](int at) { return stages(rec + (size_t)((at + 1) & 1) * nobj, 0); };
-    int at = 0;
-    if (hs_dev != nullptr) {
-        volatile int* hv = status.r.pinned;
-        for (int i = 0; i < 4; ++i) hv[i] = -1;
-        status.pending = true;   // the device writes the words until the stream drains
-        if ((rc = control(0)) || (rc = attempt(0))) return rc;
-        for (;; ++at) {
-            GP_REQUIRE(at < 100000, "like_sample_object: attempt limit reached");
-            if ((rc = control(at + 1)) || (rc = attempt(at + 1))) return rc;
-            const int want = at + 1;
-            const auto t_end = std::chrono::steady_clock::now() + std::chrono::seconds(60);
-            int v;
-            while (((v = hv[want & 3]) >> 2) != want)
-                GP_REQUIRE(std::chrono::steady_clock::now() < t_end, "like_sample_object: no status from attempt %d",
-                           want);
-            if ((v & 3) != 1) break;
-        }
-    } else {
-        if ((rc = control(0)) || (rc = attempt(0))) return rc;
-        for (;; ++at) {
-            GP_REQUIRE(at < 100000, "like_sample_object: attempt limit reached");
-            if ((rc = control(at + 1))) return rc;
-            status.pending = true;
-            GP_REQUIRE(hipMemcpyAsync(status.r.pinned, dstat, 4, hipMemcpyDeviceToHost, stream) == hipSuccess &&
-                           hipEventRecord(status.r.ev, stream) == hipSuccess, "like_sample_object: status read");
-            if ((rc = attempt(at + 1))) return rc;   // a no-op once no object runs
-            GP_REQUIRE(hipEventSynchronize(status.r.ev) == hipSuccess, "like_sample_object: status wait");
-            status.pending = false;
-            GP_REQUIRE((*status.r.pinned >> 2) == at + 1, "like_sample_object: status word of attempt %d", at + 1);
-            if ((*status.r.pinned & 3) != 1) break;
-        }
-    }
-    const OdeObjRec* fin = rec + (size_t)((at + 2) & 1) * nobj;
-    GP_REQUIRE(hipMemcpyAsync(hrec.data(), fin, sizeof(OdeObjRec) * (size_t)nobj, hipMemcpyDeviceToHost, stream) ==
-                       hipSuccess && hipStreamSynchronize(stream) == hipSuccess, "like_sample_object: final records");
-    status.pending = false;
-    for (int b = 0; b < nobj; ++b) {
-        status_out[b] = hrec[(size_t)b].status;
-        nfev_out[b] = hrec[(size_t)b].nfev;
-    }
+    const OdeObjRec* fin = nullptr;
+    if ((rc = ode_obj_solve(sv, stages, init_norms, &fin, status_out, nfev_out, nullptr))) return rc;
     // ---- the latent and the likelihood in bits. sigma_max and the log term are float32 scalars in the reference
     //      (sigma(1.0) of a float32 tensor; -9/2 log(2 pi sigma_max^2) in float32), z float64
     LikeObjFinalArgs fa = {};
@@ -535,26 +364,7 @@ extern "C" int gp_debug_like_obj_attempt(const gp_head_weights* w, const float* 
     if ((rc = ode_obj_launch_control(w, pobj, r, nullptr, nullptr, 0, 0, 6, kc, k, nobj, init, nullptr, nullptr, nullptr,
                                      0, stream)))
         return rc;
-    LikeObjArgs a = {};
-    a.w = *w;
-    a.init = init;
-    a.zrow = zrow;
+    LikeObjArgs a = like_obj_args(w, init, zrow, eps_dir, y, ynew, kslots, nullptr, rowsq, rtol, atol, rows, k);
     a.rec = r;
-    a.eps = eps_dir;
-    a.y = y;
-    a.ynew = ynew;
-    for (int j = 0; j < ODE_NK; ++j) {
-        a.k[j] = kslots[j];
-        a.e[j] = kE7[j];
-    }
-    a.rowsq = rowsq;
-    a.rtol = rtol;
-    a.atol = atol;
-    a.rows = rows;
-    a.kper = k;
-    a.nobj = nobj;
-    OdeTableau tb;
-    for (int j = 0; j < 36; ++j) tb.A[j] = kA6[j];
-    for (int j = 0; j < 6; ++j) tb.B[j] = kB6[j];
-    return like_obj_launch(a, tb, like_obj_np(w, rows_total), stream);
+    return like_obj_launch(a, ode_tableau(), like_obj_np(w, rows_total), stream);
 }

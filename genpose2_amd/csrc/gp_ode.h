@@ -3,10 +3,14 @@
 // The score agent's stage kernels live in gp_ode.hip, the energy agent's (the same stages around the gradient
 // trunk and its reverse pass) in gp_ode_energy.hip: a translation unit of their own, so that they cannot move the
 // register assignment of the kernels that were there before them. The per-object likelihood (gp_like_object.hip, its
-// own translation unit for the same reason) takes the per-object controller's record, constants and launch, the
-// tableau and the status reads of the whole-sampler entries from here.
+// own translation unit for the same reason) has its own stage, state and final kernels only: the per-object solve
+// between "the state is in y" and "the final records are on the host" is one host driver (ode_obj_solve, defined in
+// gp_ode.hip) that gp_ode_sample_object and gp_like_sample_object both call with their stage launch, and the
+// select_initial_step scalars, the init-norms kernel, the tableau and the status reads are defined once, here.
 #pragma once
 #include <cmath>
+#include <cstdlib>
+#include <functional>
 #include <mutex>
 #include <vector>
 
@@ -154,8 +158,46 @@ __device__ __forceinline__ double ode_obj_wave_sum(int n, F v) {
     return t;
 }
 
+// select_initial_step norms of every object (scipy _ivp/common.py) over its kper rows of NE entries, one wave per
+// object: scale = atol + |y0| rtol; f1 == NULL: out[3 b] = rms(y0 / scale), out[3 b + 1] = rms(f0 / scale); else
+// out[3 b + 2] = rms((f1 - f0) / scale). A row's squares are added in entry order, the rows by ode_obj_wave_sum.
+// NE 9: the sampler's (R,9) state; NE 10: the likelihood's [x (9 R) | logp (R)], a row's logp its tenth entry.
+template <int NE>
+__global__ __launch_bounds__(64) void ode_obj_init_norms_kernel(const double* __restrict__ y0,
+                                                                const double* __restrict__ f0,
+                                                                const double* __restrict__ f1, int rows, int kper,
+                                                                double atol, double rtol, double* __restrict__ out) {
+#pragma clang fp contract(off)
+    static_assert(NE == 9 || NE == 10, "nine pose entries, or those and logp");
+    const int b = blockIdx.x;
+    const size_t n9 = (size_t)rows * 9;
+    auto row = [&](int j, int which) {
+        const size_t r = (size_t)b * kper + j;
+        double sq = 0.0;
+        for (int o = 0; o < NE; ++o) {
+            const size_t e = o < 9 ? r * 9 + o : n9 + r;
+            const double sc = atol + fabs(y0[e]) * rtol;
+            const double v = which == 0 ? y0[e] / sc : (which == 1 ? f0[e] / sc : (f1[e] - f0[e]) / sc);
+            sq = o == 0 ? v * v : sq + v * v;
+        }
+        return sq;
+    };
+    const double rn = sqrt((double)kper * (double)NE);
+    if (f1 == nullptr) {
+        const double s0 = ode_obj_wave_sum(kper, [&](int j) { return row(j, 0); });
+        const double s1 = ode_obj_wave_sum(kper, [&](int j) { return row(j, 1); });
+        if (threadIdx.x == 0) {
+            out[3 * b] = sqrt(s0) / rn;
+            out[3 * b + 1] = sqrt(s1) / rn;
+        }
+    } else {
+        const double s2 = ode_obj_wave_sum(kper, [&](int j) { return row(j, 2); });
+        if (threadIdx.x == 0) out[3 * b + 2] = sqrt(s2) / rn;
+    }
+}
+
 // ------------------------------------------------------------------------------ host constants and status reads
-// (gp_ode.hip's whole-sampler entries and gp_like_object.hip's)
+// (the whole-solve entries: gp_ode.hip's, and gp_like_object.hip's through ode_obj_solve)
 // Dormand-Prince tableau exactly as scipy's RK45 class attributes (rk.py)
 static const double kA6[36] = {0, 0, 0, 0, 0, 0,
                         1.0 / 5, 0, 0, 0, 0, 0,
@@ -177,6 +219,37 @@ constexpr double kSigMin = 0.01, kBase = 50.0 / 0.01;
 static inline double diff_scale() { return sqrt(2.0 * (log(50.0) - log(0.01))); }
 // sigma(t32) as sde.py forms it for a float32 tensor: f32(0.01) * 5000^t32 (power correctly rounded)
 static inline float sigma32(float t32) { return 0.01f * (float)pow(kBase, (double)t32); }
+
+static inline OdeTableau ode_tableau(const double* A = kA6, const double* B = kB6) {
+    OdeTableau tb;
+    for (int j = 0; j < 36; ++j) tb.A[j] = A[j];
+    for (int j = 0; j < 6; ++j) tb.B[j] = B[j];
+    return tb;
+}
+
+// select_initial_step's host scalars (scipy _ivp/common.py), one definition for every whole-solve entry: they decide
+// the first step and with it every later accept and reject, so the order of the float64 operations is fixed.
+// -(0.5 g^2) of f(t0): solve_ivp hands t0 as a Python float, so ode_func's g is float32 sigma * float64 scale
+static inline double ode_coef_t0(float t32, double dscale) {
+    const double g = (double)sigma32(t32) * dscale;
+    return -(0.5 * (g * g));
+}
+// -(0.5 g^2) of every later time: a NumPy float64 t
+static inline double ode_coef(double t, double dscale) {
+    const double g = kSigMin * pow(kBase, t) * dscale;
+    return -(0.5 * (g * g));
+}
+// the first guess from d0 = rms(y0 / scale), d1 = rms(f0 / scale)
+static inline double ode_init_h0(double d0, double d1, double interval) {
+    const double h0 = (d0 < 1e-5 || d1 < 1e-5) ? 1e-6 : 0.01 * d0 / d1;
+    return fmin(h0, interval);
+}
+// the first step size; d2_raw = rms((f1 - f0) / scale), not yet divided by h0
+static inline double ode_init_h_abs(double h0, double d1, double d2_raw, double interval) {
+    const double d2 = d2_raw / h0;
+    const double h1 = (d1 <= 1e-15 && d2 <= 1e-15) ? fmax(1e-6, h0 * 1e-3) : pow(0.01 / fmax(d1, d2), 1.0 / 5.0);
+    return fmin(fmin(100 * h0, h1), interval);
+}
 
 static inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
@@ -225,6 +298,20 @@ struct StatusLease {
         if (dev != cur) (void)hipSetDevice(cur);
         return ok ? 0 : -1;
     }
+    // The four pinned words as the device addresses them, set to -1, or null when it cannot (zc_switch: or when
+    // GENPOSE2_ODE_ZC=0 asks for the event-and-copy form)
+    int* map(bool zc_switch) {
+        const char* zc = zc_switch ? getenv("GENPOSE2_ODE_ZC") : nullptr;
+        int* dev = nullptr;
+        if ((zc != nullptr && zc[0] == '0') ||
+            hipHostGetDevicePointer(reinterpret_cast<void**>(&dev), r.pinned, 0) != hipSuccess) {
+            (void)hipGetLastError();
+            return nullptr;
+        }
+        if (dev != nullptr)
+            for (int i = 0; i < 4; ++i) const_cast<volatile int*>(r.pinned)[i] = -1;
+        return dev;
+    }
     ~StatusLease() {
         if (r.pinned == nullptr || r.ev == nullptr) return;
         // an early return between the status copy and its wait leaves the copy in flight: it must land
@@ -250,6 +337,57 @@ int ode_obj_launch_control(const gp_head_weights* w, const float* pobj, const Od
                            float* init, unsigned long long* count, int* hstat, int* dstat, int n, hipStream_t stream);
 // p[0..n) = v (ode_obj_fill_kernel: the row of -0.0f)
 int ode_obj_launch_fill(float* p, int n, float v, hipStream_t stream);
+
+// What the workspaces of the per-object entries end in: the controller's buffers, byte offsets from the base
+struct OdeObjTail {
+    size_t rowsq, norms, rec, init, zrow, count, dstat;
+};
+static inline OdeObjTail ode_obj_tail_layout(size_t& off, int rows, int nobj) {
+    OdeObjTail T = {};
+    T.rowsq = off; off += align256((size_t)rows * sizeof(double));
+    T.norms = off; off += align256((size_t)nobj * 3 * sizeof(double));
+    T.rec = off; off += align256((size_t)nobj * 2 * sizeof(OdeObjRec));
+    T.init = off; off += align256((size_t)nobj * 6 * 768 * sizeof(float));
+    T.zrow = off; off += align256(768 * sizeof(float));
+    T.count = off; off += 256;
+    T.dstat = off; off += 256;
+    return T;
+}
+
+// One per-object solve (ode_obj_solve): nobj objects of k rows with `entries` state entries per row
+struct OdeObjSolve {
+    const gp_head_weights* w;
+    const float* pobj;
+    int nobj, k, entries;         // entries: 9 (pose), 10 (pose and logp): every norm runs over k * entries
+    double t0, t_bound, rtol, atol;
+    OdeObjRec* rec;               // rec[parity * nobj + b]
+    float* init;                  // (6, nobj, 768) folded rows
+    float* zrow;                  // (768), filled with -0.0f here
+    unsigned long long* count;
+    int* dstat;
+    double* norms;                // (nobj, 3)
+    double* rowsq;                // (rows) the stages' error sums
+    hipStream_t stream;
+    const char* who;              // the entry's name in messages
+    OdeObjSolve(const gp_head_weights* w_, const float* pobj_, int nobj_, int k_, int entries_, double t0_,
+                double t_bound_, double rtol_, double atol_, char* ws, const OdeObjTail& T, hipStream_t stream_,
+                const char* who_)
+        : w(w_), pobj(pobj_), nobj(nobj_), k(k_), entries(entries_), t0(t0_), t_bound(t_bound_), rtol(rtol_),
+          atol(atol_), rec(reinterpret_cast<OdeObjRec*>(ws + T.rec)), init(reinterpret_cast<float*>(ws + T.init)),
+          zrow(reinterpret_cast<float*>(ws + T.zrow)), count(reinterpret_cast<unsigned long long*>(ws + T.count)),
+          dstat(reinterpret_cast<int*>(ws + T.dstat)), norms(reinterpret_cast<double*>(ws + T.norms)),
+          rowsq(reinterpret_cast<double*>(ws + T.rowsq)), stream(stream_), who(who_) {}
+};
+// The solve of every object from "the state is in y" to "the final records are on the host": the row of -0.0f and
+// the counter, select_initial_step per object (two rounds of host-built records: upload, the slot-0 rows, one
+// evaluation, the norms, a read-back), the attempts kept one ahead of the status read (polled pinned words, or a
+// 4-byte copy and an event), and the read of the final records: *fin the device's; from the host's copy
+// status_out / nfev_out (nobj each) and *failed, whether a solve ended below the spacing of t (each may be null).
+// stages(rec, single): the entry's stage kernel on these records (single 0: an attempt; 1: K_0 = f(t, y);
+// 2: f1 = f(t, y + K_0 h)); init_norms(with_f1): its ode_obj_init_norms_kernel launch into s.norms.
+int ode_obj_solve(const OdeObjSolve& s, const std::function<int(const OdeObjRec*, int)>& stages,
+                  const std::function<int(bool)>& init_norms, const OdeObjRec** fin, int* status_out, int* nfev_out,
+                  bool* failed);
 
 // ------------------------------------------------------------------------------ host side, gp_ode_energy.hip
 // The energy agent's stages: 16-row tiles, exact fp32. Each returns gp_check_launch's status.

@@ -899,9 +899,7 @@ static int ode_auto_attempt_impl(const gp_head_weights* w, const float* pobj, in
     a.ybuf[1] = y1;
     for (int j = 0; j < ODE_NK; ++j) a.kbuf[j] = kslots[j];
     if (ode_fused()) {   // one launch per attempt (ode_attempt_kernel)
-        OdeTableau tb;
-        for (int j = 0; j < 36; ++j) tb.A[j] = tableau_a[j];
-        for (int j = 0; j < 6; ++j) tb.B[j] = b[j];
+        const OdeTableau tb = ode_tableau(tableau_a, b);
         for (int j = 0; j < ODE_NK; ++j) a.e[j] = e[j];
         a.part = part;
         if (gw) return ode_energy_launch_attempt(a, *gw, tb, stream);
@@ -1040,6 +1038,48 @@ __global__ void f32_to_f64_kernel(const float* __restrict__ in, double* __restri
 
 extern "C" size_t gp_ode_sample_workspace_size(int rows) { return rows >= 1 ? ode_sample_layout(rows).total : 0; }
 
+// The attempts of a whole solve, one enqueued ahead of the status read, for every whole-solve entry. launch(n, what)
+// enqueues attempt n's control (what & 1: decides attempt n - 1, prepares n, writes its status word) and its stages
+// (what & 2: a no-op once the solve has ended). hs_dev (StatusLease::map) non-null: the control of attempt n writes
+// 4 n + state (state 1: running) into pinned word n & 3 and the host polls it; nothing sits between a control launch
+// and its stage launch. Null: the 4-byte word at stat_src(n) is copied behind control n, with an event, ahead of
+// attempt n's stages; `numbered`: that word is 4 n + state too, else it is nonzero once the solve has ended.
+// *last + 1 is the attempt whose control saw the end: the final records are those of parity (*last + 2) & 1.
+template <typename Launch, typename Src>
+static int ode_run_attempts(StatusLease& status, const int* hs_dev, bool numbered, Launch launch, Src stat_src,
+                            const char* who, int* last) {
+    int rc, a = 0;
+    if (hs_dev != nullptr) status.pending = true;   // the device writes the words until the stream drains
+    if ((rc = launch(0, 3))) return rc;
+    for (;; ++a) {
+        GP_REQUIRE(a < 100000, "%s: attempt limit reached", who);
+        const int want = a + 1;   // its control decides attempt a
+        int v;
+        if (hs_dev != nullptr) {
+            if ((rc = launch(want, 3))) return rc;
+            volatile int* hv = status.r.pinned;
+            const auto t_end = std::chrono::steady_clock::now() + std::chrono::seconds(60);
+            while (((v = hv[want & 3]) >> 2) != want)
+                GP_REQUIRE(std::chrono::steady_clock::now() < t_end, "%s: no status from attempt %d", who, want);
+            if ((v & 3) != 1) break;
+        } else {
+            if ((rc = launch(want, 1))) return rc;
+            status.pending = true;
+            GP_REQUIRE(hipMemcpyAsync(status.r.pinned, stat_src(want), 4, hipMemcpyDeviceToHost, status.stream) ==
+                               hipSuccess && hipEventRecord(status.r.ev, status.stream) == hipSuccess,
+                       "%s: status read", who);
+            if ((rc = launch(want, 2))) return rc;
+            GP_REQUIRE(hipEventSynchronize(status.r.ev) == hipSuccess, "%s: status wait", who);
+            status.pending = false;
+            v = *status.r.pinned;
+            GP_REQUIRE(!numbered || (v >> 2) == want, "%s: status word of attempt %d", who, want);
+            if (numbered ? (v & 3) != 1 : v != 0) break;
+        }
+    }
+    *last = a;
+    return GP_OK;
+}
+
 // gw: null for the score agent; the energy agent's transposed weights otherwise (its right-hand sides, attempts
 // and denoise are gp_ode_rhs_energy, gp_ode_auto_attempt_energy and gp_ode_denoise_energy)
 static int ode_sample_impl(const gp_head_weights* w, const gp_head_grad_weights* gw, const float* pobj,
@@ -1079,91 +1119,46 @@ static int ode_sample_impl(const gp_head_weights* w, const gp_head_grad_weights*
     if ((rc = gp_check_launch("f32_to_f64_kernel"))) return rc;
 
     // ---- select_initial_step (scipy common.py), as genpose2_amd/ode.py initial_step
-    {   // f(t0): solve_ivp hands t0 as a Python float, so ode_func's g is float32 sigma * float64 scale
+    {   // f(t0)
         const float t32 = (float)t0;
-        const double g = (double)sigma32(t32) * dscale;
-        if ((rc = rhs(t32, -(0.5 * (g * g)), nullptr, nullptr, 0, 0.0, K[0]))) return rc;
+        if ((rc = rhs(t32, ode_coef_t0(t32, dscale), nullptr, nullptr, 0, 0.0, K[0]))) return rc;
     }
     if ((rc = gp_ode_init_norms(y[0], K[0], nullptr, n, atol, rtol, scal, stream))) return rc;
     double hs[3];
     GP_REQUIRE(hipMemcpyAsync(hs, scal, 2 * sizeof(double), hipMemcpyDeviceToHost, stream) == hipSuccess &&
                    hipStreamSynchronize(stream) == hipSuccess, "ode_sample: norm read");
-    const double d0 = hs[0], d1 = hs[1], interval = fabs(tf - t0);
-    double h0 = (d0 < 1e-5 || d1 < 1e-5) ? 1e-6 : 0.01 * d0 / d1;
-    h0 = fmin(h0, interval);
-    {   // f(t0 + h0 dir, y0 + h0 dir f0): a NumPy float64 time from here on
+    const double interval = fabs(tf - t0);
+    const double h0 = ode_init_h0(hs[0], hs[1], interval);
+    {   // f(t0 + h0 dir, y0 + h0 dir f0)
         const double t = t0 + h0 * dir;
-        const double g = kSigMin * pow(kBase, t) * dscale;
         const double a1 = 1.0;
         const double* kin[1] = {K[0]};
-        if ((rc = rhs((float)t, -(0.5 * (g * g)), kin, &a1, 1, h0 * dir, f1))) return rc;
+        if ((rc = rhs((float)t, ode_coef(t, dscale), kin, &a1, 1, h0 * dir, f1))) return rc;
     }
     if ((rc = gp_ode_init_norms(y[0], K[0], f1, n, atol, rtol, scal, stream))) return rc;
     GP_REQUIRE(hipMemcpyAsync(hs + 2, scal + 2, sizeof(double), hipMemcpyDeviceToHost, stream) == hipSuccess &&
                    hipStreamSynchronize(stream) == hipSuccess, "ode_sample: norm read");
-    const double d2 = hs[2] / h0;
-    const double h1 = (d1 <= 1e-15 && d2 <= 1e-15) ? fmax(1e-6, h0 * 1e-3) : pow(0.01 / fmax(d1, d2), 1.0 / 5.0);
-    const double h_abs = fmin(fmin(100 * h0, h1), interval);
 
     // ---- device-controlled attempts, one enqueued ahead of the status read
     OdeCtl c0 = {};
     c0.t = t0;
-    c0.h_abs = h_abs;
+    c0.h_abs = ode_init_h_abs(h0, hs[1], hs[2], interval);
     c0.nfev = 2;
     for (int j = 0; j < ODE_NK; ++j) c0.kidx[j] = j;
     GP_REQUIRE(hipMemcpyAsync(aws, &c0, sizeof(OdeCtl), hipMemcpyHostToDevice, stream) == hipSuccess &&
                    hipStreamSynchronize(stream) == hipSuccess, "ode_sample: controller record");
-    auto launch = [&](int a, int what) {
-        return ode_auto_attempt_impl(w, pobj, a, what, tf, dir, rtol, atol, kSigMin, kBase, dscale, y[0], y[1], K,
-                                     kA6, kB6, kE7, rows, k, nullptr, aws, aws_b, nullptr, stream, gw);
+    const char* ctl = static_cast<const char*>(aws);   // OdeCtl[2]; attempt n's control writes parity (n + 1) & 1
+    int* hs_dev = status.map(false);
+    auto launch = [&](int n, int what) {
+        return ode_auto_attempt_impl(w, pobj, n, what, tf, dir, rtol, atol, kSigMin, kBase, dscale, y[0], y[1], K,
+                                     kA6, kB6, kE7, rows, k, nullptr, aws, aws_b, hs_dev, stream, gw);
     };
-    const int rec = (int)sizeof(OdeCtl);
-    const int stat_off = (int)offsetof(OdeCtl, status);
+    auto stat_src = [&](int n) { return ctl + ((n + 1) & 1) * sizeof(OdeCtl) + offsetof(OdeCtl, status); };
     int a = 0;
-    int* hs_dev = nullptr;   // the pinned words as the device addresses them, if it can
-    if (hipHostGetDevicePointer(reinterpret_cast<void**>(&hs_dev), status.r.pinned, 0) != hipSuccess) {
-        hs_dev = nullptr;
-        (void)hipGetLastError();
-    }
-    if (hs_dev != nullptr) {
-        // polled: the control kernel of attempt n writes 4 n + (status + 1) into pinned word n & 3; nothing sits
-        // between a control launch and its stage launch (gp_ode_auto_attempt_hs)
-        volatile int* hv = status.r.pinned;
-        for (int i = 0; i < 4; ++i) hv[i] = -1;
-        auto launch_hs = [&](int n) {
-            return ode_auto_attempt_impl(w, pobj, n, 3, tf, dir, rtol, atol, kSigMin, kBase, dscale, y[0], y[1], K,
-                                         kA6, kB6, kE7, rows, k, nullptr, aws, aws_b, hs_dev, stream, gw);
-        };
-        status.pending = true;   // the device writes the words until the stream drains
-        if ((rc = launch_hs(0))) return rc;
-        for (;; ++a) {
-            GP_REQUIRE(a < 100000, "ode_sample: attempt limit reached");
-            if ((rc = launch_hs(a + 1))) return rc;   // decides attempt a, prepares and runs a + 1
-            const int want = a + 1;
-            const auto t_end = std::chrono::steady_clock::now() + std::chrono::seconds(60);
-            int v;
-            while (((v = hv[want & 3]) >> 2) != want)
-                GP_REQUIRE(std::chrono::steady_clock::now() < t_end, "ode_sample: no status from attempt %d", want);
-            if ((v & 3) - 1 != 0) break;
-        }
-    } else {
-        if ((rc = launch(0, 3))) return rc;
-        for (;; ++a) {
-            GP_REQUIRE(a < 100000, "ode_sample: attempt limit reached");
-            if ((rc = launch(a + 1, 1))) return rc;   // decides attempt a, prepares a + 1
-            const char* src = static_cast<const char*>(aws) + ((a + 2) & 1) * rec + stat_off;
-            status.pending = true;
-            GP_REQUIRE(hipMemcpyAsync(status.r.pinned, src, 4, hipMemcpyDeviceToHost, stream) == hipSuccess &&
-                           hipEventRecord(status.r.ev, stream) == hipSuccess, "ode_sample: status read");
-            if ((rc = launch(a + 1, 2))) return rc;   // attempt a + 1 (a no-op once the solve has ended)
-            GP_REQUIRE(hipEventSynchronize(status.r.ev) == hipSuccess, "ode_sample: status wait");
-            status.pending = false;
-            if (*status.r.pinned != 0) break;
-        }
-    }
+    if ((rc = ode_run_attempts(status, hs_dev, false, launch, stat_src, "ode_sample", &a))) return rc;
     OdeCtl c;
-    GP_REQUIRE(hipMemcpyAsync(&c, static_cast<const char*>(aws) + ((a + 2) & 1) * rec, sizeof(OdeCtl),
-                              hipMemcpyDeviceToHost, stream) == hipSuccess &&
+    GP_REQUIRE(hipMemcpyAsync(&c, ctl + ((a + 2) & 1) * sizeof(OdeCtl), sizeof(OdeCtl), hipMemcpyDeviceToHost,
+                              stream) == hipSuccess &&
                    hipStreamSynchronize(stream) == hipSuccess, "ode_sample: final record");
     status.pending = false;
     if (status_out) *status_out = c.status;
@@ -1527,40 +1522,6 @@ __global__ __launch_bounds__(HT) void ode_obj_control_kernel(gp_head_weights w, 
     }
 }
 
-// select_initial_step norms of every object (scipy _ivp/common.py), one wave per object: scale = atol + |y0| rtol;
-// f1 == NULL: out[3 b] = rms(y0 / scale), out[3 b + 1] = rms(f0 / scale); else out[3 b + 2] = rms((f1 - f0) / scale),
-// each over the object's k * 9 elements: a row's 9 squares in entry order, the rows by ode_obj_wave_sum.
-__global__ __launch_bounds__(64) void ode_obj_init_norms_kernel(const double* __restrict__ y0,
-                                                                const double* __restrict__ f0,
-                                                                const double* __restrict__ f1, int kper, double atol,
-                                                                double rtol, double* __restrict__ out) {
-#pragma clang fp contract(off)
-    const int b = blockIdx.x;
-    const size_t base = (size_t)b * kper * 9;
-    auto row = [&](int j, int which) {
-        double sq = 0.0;
-        for (int o = 0; o < 9; ++o) {
-            const size_t e = base + (size_t)j * 9 + o;
-            const double sc = atol + fabs(y0[e]) * rtol;
-            const double v = which == 0 ? y0[e] / sc : (which == 1 ? f0[e] / sc : (f1[e] - f0[e]) / sc);
-            sq = o == 0 ? v * v : sq + v * v;
-        }
-        return sq;
-    };
-    const double rn = sqrt((double)kper * 9.0);
-    if (f1 == nullptr) {
-        const double s0 = ode_obj_wave_sum(kper, [&](int j) { return row(j, 0); });
-        const double s1 = ode_obj_wave_sum(kper, [&](int j) { return row(j, 1); });
-        if (threadIdx.x == 0) {
-            out[3 * b] = sqrt(s0) / rn;
-            out[3 * b + 1] = sqrt(s1) / rn;
-        }
-    } else {
-        const double s2 = ode_obj_wave_sum(kper, [&](int j) { return row(j, 2); });
-        if (threadIdx.x == 0) out[3 * b + 2] = sqrt(s2) / rn;
-    }
-}
-
 // res.y[:, -1] of every object: with t_eval set and the solve finished, the dense output of the object's last
 // accepted step at te (ode_dense_kernel's expressions with the object's t_old and h = t - t_old; its K_0..K_6 and
 // y, the step's start, are in place); else its state (y_new while the accepted step is not copied, else y).
@@ -1616,9 +1577,102 @@ int ode_obj_launch_fill(float* p, int n, float v, hipStream_t stream) {
     return gp_check_launch("ode_obj_fill_kernel");
 }
 
+int ode_obj_solve(const OdeObjSolve& s, const std::function<int(const OdeObjRec*, int)>& stages,
+                  const std::function<int(bool)>& init_norms, const OdeObjRec** fin, int* status_out, int* nfev_out,
+                  bool* failed) {
+    const int nobj = s.nobj;
+    const hipStream_t stream = s.stream;
+    OdeObjRec* const rec = s.rec;
+    StatusLease status;
+    GP_REQUIRE(status.acquire(stream) == 0, "%s: pinned status word / event", s.who);
+    const double t0 = s.t0, tf = s.t_bound, dir = tf > t0 ? 1.0 : -1.0;
+    const double dscale = diff_scale();
+    // every norm of an object runs over its k rows' entries
+    const OdeConsts kc = {tf, dir, s.rtol, s.atol, kSigMin, kBase, dscale, (double)s.k * (double)s.entries, 0};
+    int rc;
+    GP_REQUIRE(hipMemsetAsync(s.count, 0, 256, stream) == hipSuccess, "%s: counter", s.who);
+    if ((rc = ode_obj_launch_fill(s.zrow, 768, -0.0f, stream))) return rc;
+
+    // ---- select_initial_step (scipy common.py) per object, with ode_sample_impl's scalar functions
+    std::vector<OdeObjRec> hrec((size_t)nobj);
+    std::vector<double> hn((size_t)nobj * 3), h0v((size_t)nobj);
+    // one evaluation on host-built records: upload, their rows of slot 0, the stage, the norms and their read-back
+    auto probe = [&](int parity, int single) -> int {
+        OdeObjRec* r = rec + (size_t)parity * nobj;
+        GP_REQUIRE(hipMemcpyAsync(r, hrec.data(), sizeof(OdeObjRec) * (size_t)nobj, hipMemcpyHostToDevice, stream) ==
+                           hipSuccess && hipStreamSynchronize(stream) == hipSuccess, "%s: records", s.who);
+        int prc;
+        if ((prc = ode_obj_launch_control(s.w, s.pobj, r, nullptr, nullptr, 0, 0, 1, kc, s.k, nobj, s.init, s.count,
+                                          nullptr, s.dstat, 0, stream)) ||
+            (prc = stages(r, single)) || (prc = init_norms(single == 2)))
+            return prc;
+        GP_REQUIRE(hipMemcpyAsync(hn.data(), s.norms, sizeof(double) * 3 * (size_t)nobj, hipMemcpyDeviceToHost,
+                                  stream) == hipSuccess && hipStreamSynchronize(stream) == hipSuccess,
+                   "%s: norm read", s.who);
+        return GP_OK;
+    };
+    {   // f(t0)
+        OdeObjRec r = {};
+        r.t = t0;
+        r.active = 1;
+        r.t32[0] = (float)t0;
+        r.sig[0] = sigma32(r.t32[0]);
+        r.coef[0] = ode_coef_t0(r.t32[0], dscale);
+        for (int b = 0; b < nobj; ++b) hrec[(size_t)b] = r;
+    }
+    if ((rc = probe(0, 1))) return rc;
+    const double interval = fabs(tf - t0);
+    for (int b = 0; b < nobj; ++b) {   // f(t0 + h0 dir, y0 + h0 dir f0)
+        const double h0 = ode_init_h0(hn[3 * (size_t)b], hn[3 * (size_t)b + 1], interval);
+        h0v[(size_t)b] = h0;
+        const double t = t0 + h0 * dir;
+        OdeObjRec& r = hrec[(size_t)b];
+        r.h = h0 * dir;
+        r.t32[0] = (float)t;
+        r.sig[0] = sigma32((float)t);
+        r.coef[0] = ode_coef(t, dscale);
+    }
+    if ((rc = probe(1, 2))) return rc;
+    for (int b = 0; b < nobj; ++b) {
+        OdeObjRec r = {};
+        r.t = t0;
+        r.h_abs = ode_init_h_abs(h0v[(size_t)b], hn[3 * (size_t)b + 1], hn[3 * (size_t)b + 2], interval);
+        r.nfev = 2;
+        hrec[(size_t)b] = r;
+    }
+    GP_REQUIRE(hipMemcpyAsync(rec, hrec.data(), sizeof(OdeObjRec) * (size_t)nobj, hipMemcpyHostToDevice, stream) ==
+                       hipSuccess && hipStreamSynchronize(stream) == hipSuccess, "%s: records", s.who);
+
+    // ---- the attempts, one enqueued ahead of the status read; the loop ends when no object runs
+    int* hs_dev = status.map(true);
+    auto launch = [&](int at, int what) -> int {
+        OdeObjRec* prepared = rec + (size_t)((at + 1) & 1) * nobj;
+        int lrc = GP_OK;
+        if (what & 1)   // decides attempt at - 1, prepares attempt at
+            lrc = ode_obj_launch_control(s.w, s.pobj, rec + (size_t)(at & 1) * nobj, prepared, s.rowsq, at > 0 ? 1 : 0, 1,
+                                         6, kc, s.k, nobj, s.init, s.count, hs_dev, s.dstat, at, stream);
+        return (lrc || !(what & 2)) ? lrc : stages(prepared, 0);
+    };
+    int at = 0;
+    if ((rc = ode_run_attempts(status, hs_dev, true, launch, [&](int) { return s.dstat; }, s.who, &at))) return rc;
+    *fin = rec + (size_t)((at + 2) & 1) * nobj;
+    GP_REQUIRE(hipMemcpyAsync(hrec.data(), *fin, sizeof(OdeObjRec) * (size_t)nobj, hipMemcpyDeviceToHost, stream) ==
+                       hipSuccess && hipStreamSynchronize(stream) == hipSuccess, "%s: final records", s.who);
+    status.pending = false;
+    bool bad = false;
+    for (int b = 0; b < nobj; ++b) {
+        if (status_out) status_out[b] = hrec[(size_t)b].status;
+        if (nfev_out) nfev_out[b] = hrec[(size_t)b].nfev;
+        bad = bad || hrec[(size_t)b].status < 0;
+    }
+    if (failed) *failed = bad;
+    return GP_OK;
+}
+
 namespace {
 struct OdeObjLayout {
-    size_t y, ynew, k[ODE_NK], f1, xout, rowsq, norms, rec, init, zrow, count, dstat, den_ws, total;
+    size_t y, ynew, k[ODE_NK], f1, xout, den_ws, total;
+    OdeObjTail tail;
 };
 OdeObjLayout ode_obj_layout(int rows, int nobj) {
     OdeObjLayout L = {};
@@ -1629,13 +1683,7 @@ OdeObjLayout ode_obj_layout(int rows, int nobj) {
     for (int j = 0; j < ODE_NK; ++j) { L.k[j] = off; off += vec; }
     L.f1 = off; off += vec;
     L.xout = off; off += vec;
-    L.rowsq = off; off += align256((size_t)rows * sizeof(double));
-    L.norms = off; off += align256((size_t)nobj * 3 * sizeof(double));
-    L.rec = off; off += align256((size_t)nobj * 2 * sizeof(OdeObjRec));
-    L.init = off; off += align256((size_t)nobj * 6 * 768 * sizeof(float));
-    L.zrow = off; off += align256(768 * sizeof(float));
-    L.count = off; off += 256;
-    L.dstat = off; off += 256;
+    L.tail = ode_obj_tail_layout(off, rows, nobj);
     L.den_ws = off; off += align256(gp_ode_workspace_size(rows));
     L.total = off;
     return L;
@@ -1663,27 +1711,17 @@ extern "C" int gp_ode_sample_object(const gp_head_weights* w, const float* pobj,
     const OdeObjLayout L = ode_obj_layout(rows, nobj);
     GP_REQUIRE(workspace_bytes >= L.total,
                "ode_sample_object: workspace too small (gp_ode_object_workspace_size_k(rows, k))");
-    StatusLease status;
-    GP_REQUIRE(status.acquire(stream) == 0, "ode_sample_object: pinned status word / event");
     char* ws = static_cast<char*>(workspace);
     auto dptr = [&](size_t off) { return reinterpret_cast<double*>(ws + off); };
-    OdeObjRec* rec = reinterpret_cast<OdeObjRec*>(ws + L.rec);   // rec[parity * nobj + b]
-    float* init = reinterpret_cast<float*>(ws + L.init);
-    float* zrow = reinterpret_cast<float*>(ws + L.zrow);
-    unsigned long long* count = reinterpret_cast<unsigned long long*>(ws + L.count);
-    int* dstat = reinterpret_cast<int*>(ws + L.dstat);
-    double* norms = dptr(L.norms);
+    const OdeObjSolve sv(w, pobj, nobj, k, 9, T0, eps, rtol, atol, ws, L.tail, stream, "ode_sample_object");
     const long long n = (long long)rows * 9;
-    const double t0 = T0, tf = eps, dir = tf > t0 ? 1.0 : -1.0;
-    const double dscale = diff_scale();
     const int nt = ode_nt(w, rows_total);   // the whole batch's tile class
     const int nwg = (rows + 16 * nt - 1) / (16 * nt);
-    const OdeConsts kc = {tf, dir, rtol, atol, kSigMin, kBase, dscale, (double)k * 9.0, 0};
 
     OdeObjArgs a = {};
     a.w = *w;
-    a.init = init;
-    a.zrow = zrow;
+    a.init = sv.init;
+    a.zrow = sv.zrow;
     a.y = dptr(L.y);
     a.ynew = dptr(L.ynew);
     for (int j = 0; j < ODE_NK; ++j) {
@@ -1691,15 +1729,13 @@ extern "C" int gp_ode_sample_object(const gp_head_weights* w, const float* pobj,
         a.e[j] = kE7[j];
     }
     a.f1 = dptr(L.f1);
-    a.rowsq = dptr(L.rowsq);
+    a.rowsq = sv.rowsq;
     a.rtol = rtol;
     a.atol = atol;
     a.rows = rows;
     a.kper = k;
     a.nobj = nobj;
-    OdeTableau tb;
-    for (int j = 0; j < 36; ++j) tb.A[j] = kA6[j];
-    for (int j = 0; j < 6; ++j) tb.B[j] = kB6[j];
+    const OdeTableau tb = ode_tableau();
     auto stages = [&](const OdeObjRec* r, int single) {
         a.rec = r;
         a.single = single;
@@ -1709,145 +1745,18 @@ extern "C" int gp_ode_sample_object(const gp_head_weights* w, const float* pobj,
         });
         return gp_check_launch("ode_obj_attempt_kernel");
     };
-    // rows of slot 0 for host-prepared records (the two select_initial_step evaluations)
-    auto rows0 = [&](const OdeObjRec* r) {
-        hipLaunchKernelGGL(ode_obj_control_kernel, dim3(nobj, ODE_OBJ_CHUNKS), dim3(HT), 0, stream, *w, pobj, r,
-                           (OdeObjRec*)nullptr, (const double*)nullptr, 0, 0, 1, kc, k, nobj, init, count,
-                           (int*)nullptr, dstat, 0);
-        return gp_check_launch("ode_obj_control_kernel<rows>");
+    auto init_norms = [&](bool with_f1) {
+        hipLaunchKernelGGL(ode_obj_init_norms_kernel<9>, dim3(nobj), dim3(64), 0, stream, (const double*)a.y,
+                           (const double*)a.k[0], (const double*)(with_f1 ? a.f1 : nullptr), rows, k, atol, rtol,
+                           sv.norms);
+        return gp_check_launch("ode_obj_init_norms_kernel");
     };
     int rc;
-    GP_REQUIRE(hipMemsetAsync(count, 0, 256, stream) == hipSuccess, "ode_sample_object: counter");
-    hipLaunchKernelGGL(ode_obj_fill_kernel, dim3(3), dim3(256), 0, stream, zrow, 768, -0.0f);
     hipLaunchKernelGGL(f32_to_f64_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, x0, a.y, n);
     if ((rc = gp_check_launch("f32_to_f64_kernel"))) return rc;
-
-    // ---- select_initial_step (scipy common.py) per object, gp_ode_sample's scalar expressions element by element
-    std::vector<OdeObjRec> hrec((size_t)nobj);
-    std::vector<double> hn((size_t)nobj * 3);
-    auto upload = [&](int parity) {
-        return hipMemcpyAsync(rec + (size_t)parity * nobj, hrec.data(), sizeof(OdeObjRec) * (size_t)nobj,
-                              hipMemcpyHostToDevice, stream) == hipSuccess &&
-               hipStreamSynchronize(stream) == hipSuccess;
-    };
-    auto norms_back = [&]() {
-        return hipMemcpyAsync(hn.data(), norms, sizeof(double) * 3 * (size_t)nobj, hipMemcpyDeviceToHost, stream) ==
-                   hipSuccess && hipStreamSynchronize(stream) == hipSuccess;
-    };
-    {   // f(t0): solve_ivp hands t0 as a Python float, so ode_func's g is float32 sigma * float64 scale
-        const float t32 = (float)t0;
-        const double g = (double)sigma32(t32) * dscale;
-        for (int b = 0; b < nobj; ++b) {
-            OdeObjRec r = {};
-            r.t = t0;
-            r.active = 1;
-            r.t32[0] = t32;
-            r.sig[0] = sigma32(t32);
-            r.coef[0] = -(0.5 * (g * g));
-            hrec[(size_t)b] = r;
-        }
-    }
-    GP_REQUIRE(upload(0), "ode_sample_object: records");
-    if ((rc = rows0(rec))) return rc;
-    if ((rc = stages(rec, 1))) return rc;
-    hipLaunchKernelGGL(ode_obj_init_norms_kernel, dim3(nobj), dim3(64), 0, stream, (const double*)a.y,
-                       (const double*)a.k[0], (const double*)nullptr, k, atol, rtol, norms);
-    if ((rc = gp_check_launch("ode_obj_init_norms_kernel"))) return rc;
-    GP_REQUIRE(norms_back(), "ode_sample_object: norm read");
-    const double interval = fabs(tf - t0);
-    std::vector<double> h0v((size_t)nobj);
-    for (int b = 0; b < nobj; ++b) {
-        const double d0 = hn[3 * (size_t)b], d1 = hn[3 * (size_t)b + 1];
-        double h0 = (d0 < 1e-5 || d1 < 1e-5) ? 1e-6 : 0.01 * d0 / d1;
-        h0 = fmin(h0, interval);
-        h0v[(size_t)b] = h0;
-        // f(t0 + h0 dir, y0 + h0 dir f0): a NumPy float64 time from here on
-        const double t = t0 + h0 * dir;
-        const double g = kSigMin * pow(kBase, t) * dscale;
-        OdeObjRec& r = hrec[(size_t)b];
-        r.h = h0 * dir;
-        r.t32[0] = (float)t;
-        r.sig[0] = sigma32((float)t);
-        r.coef[0] = -(0.5 * (g * g));
-    }
-    GP_REQUIRE(upload(1), "ode_sample_object: records");
-    if ((rc = rows0(rec + nobj))) return rc;
-    if ((rc = stages(rec + nobj, 2))) return rc;
-    hipLaunchKernelGGL(ode_obj_init_norms_kernel, dim3(nobj), dim3(64), 0, stream, (const double*)a.y,
-                       (const double*)a.k[0], (const double*)a.f1, k, atol, rtol, norms);
-    if ((rc = gp_check_launch("ode_obj_init_norms_kernel"))) return rc;
-    GP_REQUIRE(norms_back(), "ode_sample_object: norm read");
-    for (int b = 0; b < nobj; ++b) {
-        const double d1 = hn[3 * (size_t)b + 1], h0 = h0v[(size_t)b];
-        const double d2 = hn[3 * (size_t)b + 2] / h0;
-        const double h1 = (d1 <= 1e-15 && d2 <= 1e-15) ? fmax(1e-6, h0 * 1e-3) : pow(0.01 / fmax(d1, d2), 1.0 / 5.0);
-        OdeObjRec r = {};
-        r.t = t0;
-        r.h_abs = fmin(fmin(100 * h0, h1), interval);
-        r.nfev = 2;
-        hrec[(size_t)b] = r;
-    }
-    GP_REQUIRE(upload(0), "ode_sample_object: records");
-
-    // ---- the attempts, one enqueued ahead of the status read; the loop ends when no object runs
-    int* hs_dev = nullptr;   // the pinned words as the device addresses them, if it can
-    {
-        const char* zc = getenv("GENPOSE2_ODE_ZC");
-        if ((zc != nullptr && zc[0] == '0') ||
-            hipHostGetDevicePointer(reinterpret_cast<void**>(&hs_dev), status.r.pinned, 0) != hipSuccess) {
-            hs_dev = nullptr;
-            (void)hipGetLastError();
-        }
-    }
-    auto control = [&](int at) {   // decides attempt at - 1, prepares attempt at
-        hipLaunchKernelGGL(ode_obj_control_kernel, dim3(nobj, ODE_OBJ_CHUNKS), dim3(HT), 0, stream, *w, pobj,
-                           (const OdeObjRec*)(rec + (size_t)(at & 1) * nobj), rec + (size_t)((at + 1) & 1) * nobj,
-                           (const double*)a.rowsq, at > 0 ? 1 : 0, 1, 6, kc, k, nobj, init, count, hs_dev, dstat, at);
-        return gp_check_launch("ode_obj_control_kernel");
-    };
-    auto attempt = [&](int at) { return stages(rec + (size_t)((at + 1) & 1) * nobj, 0); };
-    int at = 0;
-    if (hs_dev != nullptr) {
-        volatile int* hv = status.r.pinned;
-        for (int i = 0; i < 4; ++i) hv[i] = -1;
-        status.pending = true;   // the device writes the words until the stream drains
-        if ((rc = control(0)) || (rc = attempt(0))) return rc;
-        for (;; ++at) {
-            GP_REQUIRE(at < 100000, "ode_sample_object: attempt limit reached");
-            if ((rc = control(at + 1)) || (rc = attempt(at + 1))) return rc;
-            const int want = at + 1;
-            const auto t_end = std::chrono::steady_clock::now() + std::chrono::seconds(60);
-            int v;
-            while (((v = hv[want & 3]) >> 2) != want)
-                GP_REQUIRE(std::chrono::steady_clock::now() < t_end, "ode_sample_object: no status from attempt %d",
-                           want);
-            if ((v & 3) != 1) break;
-        }
-    } else {
-        if ((rc = control(0)) || (rc = attempt(0))) return rc;
-        for (;; ++at) {
-            GP_REQUIRE(at < 100000, "ode_sample_object: attempt limit reached");
-            if ((rc = control(at + 1))) return rc;
-            status.pending = true;
-            GP_REQUIRE(hipMemcpyAsync(status.r.pinned, dstat, 4, hipMemcpyDeviceToHost, stream) == hipSuccess &&
-                           hipEventRecord(status.r.ev, stream) == hipSuccess, "ode_sample_object: status read");
-            if ((rc = attempt(at + 1))) return rc;   // a no-op once no object runs
-            GP_REQUIRE(hipEventSynchronize(status.r.ev) == hipSuccess, "ode_sample_object: status wait");
-            status.pending = false;
-            GP_REQUIRE((*status.r.pinned >> 2) == at + 1, "ode_sample_object: status word of attempt %d", at + 1);
-            if ((*status.r.pinned & 3) != 1) break;
-        }
-    }
-    const OdeObjRec* fin = rec + (size_t)((at + 2) & 1) * nobj;
-    GP_REQUIRE(hipMemcpyAsync(hrec.data(), fin, sizeof(OdeObjRec) * (size_t)nobj, hipMemcpyDeviceToHost, stream) ==
-                       hipSuccess && hipStreamSynchronize(stream) == hipSuccess, "ode_sample_object: final records");
-    status.pending = false;
+    const OdeObjRec* fin = nullptr;
     bool failed = false;
-    for (int b = 0; b < nobj; ++b) {
-        if (status_out) status_out[b] = hrec[(size_t)b].status;
-        if (nfev_out) nfev_out[b] = hrec[(size_t)b].nfev;
-        failed = failed || hrec[(size_t)b].status < 0;
-    }
+    if ((rc = ode_obj_solve(sv, stages, init_norms, &fin, status_out, nfev_out, &failed))) return rc;
     GP_REQUIRE(!(failed && steps > 0),
                "ode_sample_object: RK45 failed (step size below the spacing of t) with t_eval set: the collected "
                "t_eval outputs need the host controller (genpose2_amd/ode.py rk45_drive)");
@@ -1869,7 +1778,7 @@ extern "C" int gp_ode_sample_object(const gp_head_weights* w, const float* pobj,
     // ---- denoise (samplers.py:240-249) with eps's scalars: a float32 1-element tensor for g
     const float te = (float)eps;
     const float sig = sigma32(te);
-    const float g = sig * (float)dscale;
+    const float g = sig * (float)diff_scale();
     const float step = (float)((1.0 - eps) / (steps > 0 ? steps : 1000));
     return ode_denoise_impl(w, pobj, te, sig, g * g, step, fa.out, rows, k, rows_total, pts_center, pose, q,
                             ws + L.den_ws, gp_ode_workspace_size(rows), stream);

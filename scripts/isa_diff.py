@@ -29,7 +29,7 @@ def kernels(so):
             ins = []
             for line in body.split("\n"):
                 code = re.sub(r"<[^>]*>", "", line.split("//")[0]).strip()
-                if code:
+                if code and code != "...":   # "...": zero padding up to the next symbol's alignment
                     ins.append(code)
             out[fn] = ins
     return out
