@@ -224,6 +224,9 @@ _SIGS: Dict[str, tuple] = {
     "gp_bbox_length": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "gp_rank_aggregate": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_int, c_void_p, c_void_p,
                                   c_void_p, c_void_p]),
+    "gp_rank_aggregate_modes": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_int, c_int,
+                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "gp_frame_mask_stats": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "gp_frame_crop_boxes": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "gp_frame_objects_workspace_size": (c_size_t, [c_int, c_int]),

@@ -5,6 +5,8 @@
 * ``aggregate_pose``        <- runners/evaluation_single.py:160-219 (top retain_ratio*K, quaternion
   average, optional DBSCAN re-average of the largest cluster, mean translation, 4x4)
 
+* ``aggregate_modes``       the same, with every rotation cluster kept (pose hypotheses: ``PoseModes``)
+
 Both run as ONE launch of ``gp_rank_aggregate`` (csrc/gp_aggregate.hip) over the whole batch; the
 reference does a per-object host loop with .cpu().numpy() round trips and sklearn DBSCAN. The torch
 rotation helpers below serve ``PoseNet.pred_func(return_average_res=True)`` (posenet_agent.py:560),
@@ -13,7 +15,8 @@ which the reference also runs as torch ops on device.
 from __future__ import annotations
 
 import ctypes
-from typing import Optional, Tuple
+from dataclasses import dataclass, fields
+from typing import List, Optional, Sequence, Tuple
 
 import torch
 
@@ -107,3 +110,95 @@ def aggregate_pose(pred_pose: torch.Tensor, pred_energy: torch.Tensor, retain_ra
     agg, _, _ = _rank_aggregate(pred_pose.to(torch.float32), pred_energy.to(torch.float32), keep, clustering,
                                 clustering_eps, int(clustering_minpts * keep), False)
     return agg
+
+
+# ============================================================================ pose hypotheses
+MAX_MODES = 8   # AGG_MAXMODES (csrc/gp_aggregate.hip)
+
+
+@dataclass
+class PoseModes:
+    """Every rotation cluster of each object's kept candidates (``gp_rank_aggregate_modes``), device tensors.
+
+    With L = ``n_clusters`` the slots hold the clusters in descending member count (ties: the lower DBSCAN label),
+    so slot 0 is the cluster ``aggregate_pose`` averages; ``max(1, min(L, M))`` slots are filled, slot 0 with the
+    whole kept set when L = 0, and the others are zeros with count 0."""
+    aggregated: torch.Tensor    # (B,4,4) aggregate_pose's result, the same bits
+    mode_pose: torch.Tensor     # (B,M,4,4) R: the members' quaternion average; t: the mean of their own translations
+    mode_count: torch.Tensor    # (B,M) int32
+    mode_energy: torch.Tensor   # (B,M) mean rotation energy of the members
+    mode_spread: torch.Tensor   # (B,M) mean 1 - <q_r, q_mode>^2 (the unit of clustering_eps)
+    n_clusters: torch.Tensor    # (B,) int32, not capped by M
+    noise_count: torch.Tensor   # (B,) int32
+    nearest: torch.Tensor       # (B,) int32 slot nearest to prev_rot, -1 without one
+
+    @classmethod
+    def empty(cls, bs: int, max_modes: int, device) -> "PoseModes":
+        """Uninitialised outputs for ``bs`` objects and ``max_modes`` slots."""
+        f32, i32 = dict(dtype=torch.float32, device=device), dict(dtype=torch.int32, device=device)
+        M = max(int(max_modes), 0)
+        return cls(aggregated=torch.empty((bs, 4, 4), **f32), mode_pose=torch.empty((bs, M, 4, 4), **f32),
+                   mode_count=torch.empty((bs, M), **i32), mode_energy=torch.empty((bs, M), **f32),
+                   mode_spread=torch.empty((bs, M), **f32), n_clusters=torch.empty((bs,), **i32),
+                   noise_count=torch.empty((bs,), **i32), nearest=torch.empty((bs,), **i32))
+
+    def slice(self, lo: int, hi: int) -> "PoseModes":
+        """Objects lo..hi-1 (views)."""
+        return PoseModes(**{f.name: getattr(self, f.name)[lo:hi] for f in fields(self)})
+
+    def split(self, offsets: Sequence[int]) -> List["PoseModes"]:
+        """One PoseModes per frame of a batch with these ``frame_offsets``."""
+        offsets = [int(o) for o in offsets]
+        return [self.slice(lo, hi) for lo, hi in zip(offsets[:-1], offsets[1:])]
+
+    def follow(self, pose: torch.Tensor) -> torch.Tensor:
+        """``pose`` (B,4,4) with each object's rotation replaced by that of its ``nearest`` slot (a device gather,
+        no host read); an object without a nearest slot (-1) keeps its rotation, and every translation stays."""
+        idx = self.nearest.to(torch.int64)
+        picked = torch.gather(self.mode_pose, 1, idx.clamp(min=0).view(-1, 1, 1, 1).expand(-1, 1, 4, 4))[:, 0]
+        out = pose.clone()
+        out[:, :3, :3] = torch.where((idx >= 0).view(-1, 1, 1), picked[:, :3, :3], pose[:, :3, :3])
+        return out
+
+
+def aggregate_modes(pred_pose: torch.Tensor, pred_energy: torch.Tensor, retain_ratio: float = 0.4,
+                    clustering: int = 1, clustering_eps: float = 0.05, clustering_minpts: float = 0.1667,
+                    retain_num: Optional[int] = None, max_modes: int = 4,
+                    prev_rot: Optional[torch.Tensor] = None) -> PoseModes:
+    """``aggregate_pose`` and, in the same launch, every rotation cluster it found -> ``PoseModes``.
+
+    ``max_modes`` M is 1..8; ``prev_rot`` (B,3,3) selects ``nearest`` (see ``PoseModes``)."""
+    K = pred_pose.shape[1]
+    keep = int(K * retain_ratio) if retain_num is None else int(retain_num)
+    if keep < 1:
+        raise ValueError(f"retain_ratio {retain_ratio} keeps no candidate of K={K}")
+    if keep > K:
+        raise ValueError(f"retain_num {keep} exceeds the {K} candidates per object")
+    modes, _, _ = _rank_aggregate_modes(pred_pose.to(torch.float32), pred_energy.to(torch.float32), keep, clustering,
+                                        clustering_eps, int(clustering_minpts * keep), max_modes, prev_rot, False)
+    return modes
+
+
+def _rank_aggregate_modes(poses: torch.Tensor, energy: torch.Tensor, retain: int, clustering: int, eps: float,
+                          min_samples: int, max_modes: int, prev_rot: Optional[torch.Tensor], want_sorted: bool):
+    """-> (PoseModes, sorted_pose or None, sorted_energy or None): one launch of gp_rank_aggregate_modes."""
+    poses = require_device_tensor(poses, "pred_pose")
+    energy = require_device_tensor(energy, "pred_energy")
+    bs, K = poses.shape[:2]
+    if tuple(poses.shape) != (bs, K, 9) or tuple(energy.shape) != (bs, K, 2):
+        raise ValueError(f"pred_pose {tuple(poses.shape)} / pred_energy {tuple(energy.shape)}: need (B,K,9)/(B,K,2)")
+    M = int(max_modes)
+    if prev_rot is not None:
+        prev_rot = require_device_tensor(prev_rot.to(torch.float32), "prev_rot")
+        if tuple(prev_rot.shape) != (bs, 3, 3):
+            raise ValueError(f"prev_rot must be ({bs},3,3), got {tuple(prev_rot.shape)}")
+    out = PoseModes.empty(bs, M, poses.device)   # an invalid M still reaches the library, which reports it
+    sp = torch.empty_like(poses) if want_sorted else None
+    se = torch.empty_like(energy) if want_sorted else None
+    vp = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else None)  # noqa: E731
+    _lib.check(_lib.load().gp_rank_aggregate_modes(
+        vp(poses), vp(energy), bs, K, retain, int(bool(clustering)), float(eps), int(min_samples), M, vp(prev_rot),
+        vp(out.aggregated), vp(sp), vp(se), vp(out.mode_pose), vp(out.mode_count), vp(out.mode_energy),
+        vp(out.mode_spread), vp(out.n_clusters), vp(out.noise_count), vp(out.nearest),
+        ctypes.c_void_p(stream_handle(poses.device))), "rank_aggregate_modes")
+    return out, sp, se

@@ -15,6 +15,10 @@
 //     clusters grown depth-first from core points in index order), re-average of the largest
 //     cluster (first label on count ties, numpy argmax);
 //  5. mean translation, 4x4 [R t; 0 1].
+//
+// gp_rank_aggregate_modes is the same launch with step 4 finished: every cluster's average, count, mean energy
+// and spread (pose hypotheses), and the slot nearest to a previous rotation. The two kernels share their body
+// (gp_aggregate_body.h).
 #include "gp_common.h"
 
 constexpr int AGG_THREADS = 64;
@@ -129,162 +133,71 @@ struct AggSmem {
     float qavg[4];
 };
 
+// Pose hypotheses (gp_rank_aggregate_modes): every DBSCAN cluster of the kept rotations, not only the
+// largest. The LDS of the modes kernel is AggSmem followed by ModeSmem.
+constexpr int AGG_MAXMODES = 8;
+
+struct ModeSmem {
+    int nlab;                        // L: clusters DBSCAN found (0 without clustering)
+    int lcount[AGG_MAXKEEP];         // members per label
+    int slot_label[AGG_MAXMODES];    // label behind slot m (descending count, ties -> lower label)
+    float mq[AGG_MAXMODES][4];       // mode quaternions
+    float mt[AGG_MAXMODES][3];       // mode translations
+};
+
+struct ModeArgs {
+    int max_modes;
+    const float* prev_rot;   // (B,3,3) or null
+    float* mode_pose;        // (B,M,4,4)
+    int* mode_count;         // (B,M)
+    float* mode_energy;      // (B,M)
+    float* mode_spread;      // (B,M)
+    int* n_clusters;         // (B,)
+    int* noise_count;        // (B,)
+    int* nearest;            // (B,)
+};
+
+// Per-mode means that have no counterpart in the reference's aggregate: the members' own translations,
+// their rotation energies and 1 - <q_r, q_mode>^2, each an fp32 sum in rank order over the count.
+// sel < 0: every kept candidate is a member (no cluster: the reference's fallback).
+__device__ __forceinline__ void mode_means(const AggSmem& sm, const float* P, const float* E, int keep, int sel,
+                                           int count, const float* qm, float* t, float* en, float* spread) {
+#pragma clang fp contract(off)
+    float t0 = 0.f, t1 = 0.f, t2 = 0.f, e = 0.f, s = 0.f;
+    for (int r = 0; r < keep; ++r) {
+        if (sel >= 0 && sm.label[r] != sel) continue;
+        const int c = sm.ord_rot[r];
+        t0 += P[9 * c + 6];
+        t1 += P[9 * c + 7];
+        t2 += P[9 * c + 8];
+        e += E[2 * c];
+        const float dot = ((sm.q[r][0] * qm[0] + sm.q[r][1] * qm[1]) + sm.q[r][2] * qm[2]) + sm.q[r][3] * qm[3];
+        s += 1.f - dot * dot;
+    }
+    const float n = (float)count;
+    t[0] = t0 / n;
+    t[1] = t1 / n;
+    t[2] = t2 / n;
+    *en = e / n;
+    *spread = s / n;
+}
+
 __global__ __launch_bounds__(AGG_THREADS) void rank_aggregate_kernel(
     const float* __restrict__ poses, const float* __restrict__ energy, int K, int keep, int clustering,
     float eps, int min_samples, float* __restrict__ agg, float* __restrict__ sorted_pose,
     float* __restrict__ sorted_energy) {
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    AggSmem& sm = *reinterpret_cast<AggSmem*>(smem_raw);
-    const int b = blockIdx.x, tid = threadIdx.x;
-    const float* P = poses + (size_t)b * K * 9;
-    const float* E = energy + (size_t)b * K * 2;
-    // ---- 1. descending ranks, ties by lower index (stable); a total order, so the ranks are a
-    //         permutation whatever the energies hold (precedes(): NaN first, as torch.sort orders it)
-    for (int i = tid; i < K; i += AGG_THREADS) {
-        const float er = E[2 * i], et = E[2 * i + 1];
-        int rr = 0, rt = 0;
-        for (int j = 0; j < K; ++j) {
-            rr += precedes(E[2 * j], j, er, i);
-            rt += precedes(E[2 * j + 1], j, et, i);
-        }
-        sm.rank_rot[i] = rr;
-        sm.rank_tr[i] = rt;
-    }
-    __syncthreads();
-    for (int i = tid; i < K; i += AGG_THREADS) {
-        if (sm.rank_rot[i] < keep) sm.ord_rot[sm.rank_rot[i]] = i;
-        if (sm.rank_tr[i] < keep) sm.ord_tr[sm.rank_tr[i]] = i;
-        if (sorted_pose) {  // sorted_poses: rotation part by rotation rank, translation by translation rank
-            float* o = sorted_pose + ((size_t)b * K + sm.rank_rot[i]) * 9;
-            for (int c = 0; c < 6; ++c) o[c] = P[9 * i + c];
-            float* ot = sorted_pose + ((size_t)b * K + sm.rank_tr[i]) * 9;
-            for (int c = 6; c < 9; ++c) ot[c] = P[9 * i + c];
-        }
-        if (sorted_energy) {
-            sorted_energy[((size_t)b * K + sm.rank_rot[i]) * 2 + 0] = E[2 * i];
-            sorted_energy[((size_t)b * K + sm.rank_tr[i]) * 2 + 1] = E[2 * i + 1];
-        }
-    }
-    __syncthreads();
-    // ---- 2./3. quaternions of the kept rotations
-    for (int r = tid; r < keep; r += AGG_THREADS) {
-        float v[6];
-        for (int c = 0; c < 6; ++c) v[c] = P[9 * sm.ord_rot[r] + c];
-        float q[4];
-        rot6_to_quat(v, q);
-        const float sg = q[0] > 0.f ? 1.f : -1.f;   // ((Q[..., 0:1] > 0).float() - 0.5) * 2
-        for (int c = 0; c < 4; ++c) {
-            sm.q[r][c] = q[c];
-            sm.qo[r][c] = sg * q[c];
-        }
-    }
-    __syncthreads();
-    if (tid == 0) {
-        // average_quaternion_batch with uniform weights: A = sum_r w qo qo^T / sum w
-        const float w = 1.0f / (float)keep;
-        float wsum = 0.f;
-        for (int r = 0; r < keep; ++r) wsum += w;
-        double A[4][4];
-        for (int i = 0; i < 4; ++i)
-            for (int j = 0; j < 4; ++j) {
-                float acc = 0.f;
-                for (int r = 0; r < keep; ++r) acc += (sm.qo[r][i] * sm.qo[r][j]) * w;
-                A[i][j] = (double)(acc / wsum);
-            }
-        top_eigvec4(A, sm.qavg);
-    }
-    // ---- 4. DBSCAN over rows of D = 1 - <qi, qj>^2
-    if (clustering) {
-        for (int e = tid; e < keep * keep; e += AGG_THREADS) {
-            const int i = e / keep, j = e - i * keep;
-            const float dot = ((sm.q[i][0] * sm.q[j][0] + sm.q[i][1] * sm.q[j][1]) + sm.q[i][2] * sm.q[j][2]) +
-                              sm.q[i][3] * sm.q[j][3];
-            sm.D[i][j] = 1.f - dot * dot;
-        }
-        __syncthreads();
-        for (int e = tid; e < keep * keep; e += AGG_THREADS) {
-            const int i = e / keep, j = e - i * keep;
-            double d2 = 0.0;
-            for (int c = 0; c < keep; ++c) {
-                const double df = (double)sm.D[i][c] - (double)sm.D[j][c];
-                d2 += df * df;
-            }
-            sm.adj[i][j] = sqrt(d2) <= (double)eps;
-        }
-        __syncthreads();
-        for (int i = tid; i < keep; i += AGG_THREADS) {
-            int cnt = 0;
-            for (int j = 0; j < keep; ++j) cnt += sm.adj[i][j];
-            sm.ncount[i] = cnt;
-            sm.label[i] = -1;
-        }
-        __syncthreads();
-        if (tid == 0) {
-            // -1 unvisited, -2 queued; membership does not depend on the expansion order
-            int nlab = 0;
-            for (int i = 0; i < keep; ++i) {
-                if (sm.label[i] != -1 || sm.ncount[i] < min_samples) continue;
-                int top = 0;
-                sm.stack[top++] = i;
-                sm.label[i] = -2;
-                while (top > 0) {
-                    const int p = sm.stack[--top];
-                    sm.label[p] = nlab;
-                    if (sm.ncount[p] < min_samples) continue;   // border point: not expanded
-                    for (int j = 0; j < keep; ++j)
-                        if (sm.label[j] == -1 && sm.adj[p][j]) {
-                            sm.label[j] = -2;
-                            sm.stack[top++] = j;
-                        }
-                }
-                ++nlab;
-            }
-            if (nlab > 0) {
-                int best = 0, bestc = -1;
-                for (int l = 0; l < nlab; ++l) {
-                    int c = 0;
-                    for (int i = 0; i < keep; ++i) c += sm.label[i] == l;
-                    if (c > bestc) { bestc = c; best = l; }
-                }
-                const float w = 1.0f / (float)bestc;
-                float wsum = 0.f;
-                for (int r = 0; r < bestc; ++r) wsum += w;
-                double A[4][4];
-                for (int i = 0; i < 4; ++i)
-                    for (int j = 0; j < 4; ++j) {
-                        float acc = 0.f;
-                        for (int r = 0; r < keep; ++r)
-                            if (sm.label[r] == best) acc += (sm.qo[r][i] * sm.qo[r][j]) * w;
-                        A[i][j] = (double)(acc / wsum);
-                    }
-                top_eigvec4(A, sm.qavg);
-            }
-        }
-    }
-    __syncthreads();
-    // ---- 5. 4x4 [R t; 0 1]
-    if (tid < 16) {
-        const int r = tid >> 2, c = tid & 3;
-        float v;
-        if (r == 3) {
-            v = c == 3 ? 1.f : 0.f;
-        } else if (c == 3) {
-            float acc = 0.f;
-            for (int k = 0; k < keep; ++k) acc += P[9 * sm.ord_tr[k] + 6 + r];
-            v = acc / (float)keep;
-        } else {  // quaternion_to_matrix (rotation_conversions.py:41-70)
-            const float qr = sm.qavg[0], qi = sm.qavg[1], qj = sm.qavg[2], qk = sm.qavg[3];
-            const float two_s = 2.0f / (((qr * qr + qi * qi) + qj * qj) + qk * qk);
-            const float m[9] = {1 - two_s * (qj * qj + qk * qk), two_s * (qi * qj - qk * qr), two_s * (qi * qk + qj * qr),
-                                two_s * (qi * qj + qk * qr), 1 - two_s * (qi * qi + qk * qk), two_s * (qj * qk - qi * qr),
-                                two_s * (qi * qk - qj * qr), two_s * (qj * qk + qi * qr), 1 - two_s * (qi * qi + qj * qj)};
-            v = 0.f;
-#pragma unroll
-            for (int e = 0; e < 9; ++e)
-                if (e == r * 3 + c) v = m[e];
-        }
-        agg[(size_t)b * 16 + tid] = v;
-    }
+#define AGG_MODES 0
+#include "gp_aggregate_body.h"
+#undef AGG_MODES
+}
+
+__global__ __launch_bounds__(AGG_THREADS) void rank_aggregate_modes_kernel(
+    const float* __restrict__ poses, const float* __restrict__ energy, int K, int keep, int clustering,
+    float eps, int min_samples, float* __restrict__ agg, float* __restrict__ sorted_pose,
+    float* __restrict__ sorted_energy, ModeArgs ma) {
+#define AGG_MODES 1
+#include "gp_aggregate_body.h"
+#undef AGG_MODES
 }
 
 extern "C" int gp_rank_aggregate(const float* poses, const float* energy, int b, int k, int retain, int clustering,
@@ -304,6 +217,34 @@ extern "C" int gp_rank_aggregate(const float* poses, const float* energy, int b,
     hipLaunchKernelGGL(rank_aggregate_kernel, dim3(b), dim3(AGG_THREADS), lds, stream, poses, energy, k, retain,
                        clustering, eps, min_samples, aggregated, sorted_pose, sorted_energy);
     return gp_check_launch("rank_aggregate_kernel");
+}
+
+extern "C" int gp_rank_aggregate_modes(const float* poses, const float* energy, int b, int k, int retain,
+                                       int clustering, float eps, int min_samples, int max_modes,
+                                       const float* prev_rot, float* aggregated, float* sorted_pose,
+                                       float* sorted_energy, float* mode_pose, int* mode_count, float* mode_energy,
+                                       float* mode_spread, int* n_clusters, int* noise_count, int* nearest,
+                                       hipStream_t stream) {
+    GP_REQUIRE(max_modes >= 1 && max_modes <= AGG_MAXMODES, "rank_aggregate_modes: need 1 <= max_modes <= %d (%d)",
+               AGG_MAXMODES, max_modes);
+    GP_REQUIRE(b == 0 || (poses && energy && aggregated), "rank_aggregate_modes: null pointer");
+    GP_REQUIRE(b == 0 || (mode_pose && mode_count && mode_energy && mode_spread && n_clusters && noise_count && nearest),
+               "rank_aggregate_modes: null mode output");
+    GP_REQUIRE(b >= 0 && k >= 1 && k <= AGG_MAXK, "rank_aggregate_modes: need 1 <= k <= %d (k=%d)", AGG_MAXK, k);
+    GP_REQUIRE(retain >= 1 && retain <= k && retain <= AGG_MAXKEEP,
+               "rank_aggregate_modes: need 1 <= retain <= min(k, %d)", AGG_MAXKEEP);
+    GP_REQUIRE(!clustering || min_samples >= 1, "rank_aggregate_modes: DBSCAN needs min_samples >= 1");
+    if (!b) return GP_OK;
+    const size_t lds = sizeof(AggSmem) + sizeof(ModeSmem);
+    if (lds > 160 * 1024) {
+        gp_set_error("rank_aggregate_modes: LDS %zu", lds);
+        return GP_ERR_UNSUPPORTED;
+    }
+    const ModeArgs ma{max_modes, prev_rot, mode_pose, mode_count, mode_energy, mode_spread, n_clusters, noise_count,
+                      nearest};
+    hipLaunchKernelGGL(rank_aggregate_modes_kernel, dim3(b), dim3(AGG_THREADS), lds, stream, poses, energy, k, retain,
+                       clustering, eps, min_samples, aggregated, sorted_pose, sorted_energy, ma);
+    return gp_check_launch("rank_aggregate_modes_kernel");
 }
 
 // ============================================================================ stage glue

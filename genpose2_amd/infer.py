@@ -14,6 +14,7 @@ from typing import Dict, List, Optional, Sequence, Tuple, Union
 import torch
 
 from . import arch, device as dev
+from .aggregate import MAX_MODES, PoseModes
 from .config import GenPoseConfig
 from .frontend import InferDataset, InferFrames
 from .runner import EvaluationPipeline
@@ -77,6 +78,25 @@ class GenPose2:
         ``prev_pose`` (B,4,4) (or the reference's one-element list of it) warm-starts the sampler at
         [R[:, 0] | R[:, 1] | t - pts_center]; the start time is ``tracking_T0`` only when ``tracking`` is set as
         well, else cfg.T0 -- as the reference does."""
+        return self._inference(data, prev_pose, tracking, tracking_T0)[:2]
+
+    @torch.no_grad()
+    def inference_modes(self, data: Union[InferDataset, Dict[str, torch.Tensor]], prev_pose=None,
+                        tracking: bool = False, tracking_T0: float = 0.15, max_modes: int = 4,
+                        follow_prev: bool = False) -> Tuple[torch.Tensor, torch.Tensor, PoseModes]:
+        """``inference`` with the pose hypotheses -> (final_pose, final_length, ``aggregate.PoseModes``): up to
+        ``max_modes`` (1..8) rotation clusters per object, from the aggregation's own launch.
+
+        With ``follow_prev`` and a ``prev_pose``, each object's final rotation is that of the slot nearest to its
+        previous rotation (``PoseModes.nearest``, picked on the device) and the size is estimated in that frame;
+        the translation stays the aggregated one. Without it the first two results are ``inference``'s bits."""
+        if not 1 <= int(max_modes) <= MAX_MODES:
+            raise ValueError(f"max_modes must be 1..{MAX_MODES}, got {max_modes}")
+        return self._inference(data, prev_pose, tracking, tracking_T0, int(max_modes), follow_prev)
+
+    def _inference(self, data, prev_pose, tracking: bool, tracking_T0: float, max_modes: int = 0,
+                   follow_prev: bool = False):
+        """-> (final_pose, final_length, PoseModes or None): the body of ``inference`` and ``inference_modes``."""
         if self.cfg.dino == "pointwise" and hasattr(data, "get_objects") and hasattr(data, "_img_size"):
             self.check_pointwise_size(data._img_size, data._img_size)   # before the front end launches anything
         batch = data.get_objects() if hasattr(data, "get_objects") else data
@@ -86,7 +106,8 @@ class GenPose2:
         pts = batch["pts"]
         B = int(pts.shape[0])
         if B == 0:
-            return pts.new_zeros((0, 4, 4)), pts.new_zeros((0, 3))
+            return pts.new_zeros((0, 4, 4)), pts.new_zeros((0, 3)), \
+                (PoseModes.empty(0, max_modes, pts.device) if max_modes else None)
         init_x = None
         if prev_pose is not None:
             if isinstance(prev_pose, (list, tuple)):
@@ -99,10 +120,15 @@ class GenPose2:
             init_x = pose_representation(prev_pose)
             init_x[:, -3:] -= batch["pts_center"]
         T0 = tracking_T0 if tracking and prev_pose is not None else None
-        out = self.pipeline.run(batch, init_x=init_x, T0=T0, energy_T=None)
+        if max_modes:
+            prev_rot = prev_pose[:, :3, :3].contiguous() if prev_pose is not None else None
+            out = self.pipeline.run(batch, init_x=init_x, T0=T0, energy_T=None, max_modes=max_modes,
+                                    prev_rot=prev_rot, follow_prev=follow_prev)
+        else:
+            out = self.pipeline.run(batch, init_x=init_x, T0=T0, energy_T=None)
         final_pose = out.aggregated
         length = out.length if out.length is not None else dev.bbox_length(pts, final_pose)
-        return final_pose, length
+        return final_pose, length, out.modes
 
     @torch.no_grad()
     def inference_frames(self, data: Union[InferFrames, Dict[str, torch.Tensor]],
@@ -122,6 +148,26 @@ class GenPose2:
         and the Langevin step size are taken over the whole batch). Under either coupling an object's prior noise
         is its rows of the whole call's draw: to reproduce a frame's objects in a call of their own, give the score
         agent ``object_window = (B, frame_offsets[f])``."""
+        batch, offsets, prev_pose = self._frames_batch(data, prev_pose)
+        pose, length, _ = self._inference(batch, prev_pose, tracking, tracking_T0)
+        return [(pose[lo:hi], length[lo:hi]) for lo, hi in zip(offsets[:-1], offsets[1:])]
+
+    @torch.no_grad()
+    def inference_frames_modes(self, data: Union[InferFrames, Dict[str, torch.Tensor]],
+                               prev_pose: Optional[Sequence[torch.Tensor]] = None, tracking: bool = False,
+                               tracking_T0: float = 0.15, max_modes: int = 4, follow_prev: bool = False
+                               ) -> List[Tuple[torch.Tensor, torch.Tensor, PoseModes]]:
+        """``inference_modes`` for F frames in one call, as ``inference_frames`` does it for ``inference``: a list
+        of F triples (final_pose, final_length, PoseModes), the hypotheses split by ``frame_offsets`` too."""
+        if not 1 <= int(max_modes) <= MAX_MODES:
+            raise ValueError(f"max_modes must be 1..{MAX_MODES}, got {max_modes}")
+        batch, offsets, prev_pose = self._frames_batch(data, prev_pose)
+        pose, length, modes = self._inference(batch, prev_pose, tracking, tracking_T0, int(max_modes), follow_prev)
+        return [(pose[lo:hi], length[lo:hi], m)
+                for lo, hi, m in zip(offsets[:-1], offsets[1:], modes.split(offsets))]
+
+    def _frames_batch(self, data, prev_pose):
+        """-> (the batch of all frames, its frame offsets, prev_pose as one (B,4,4) tensor or None)."""
         if self.cfg.dino == "pointwise" and hasattr(data, "get_objects") and hasattr(data, "_img_size"):
             self.check_pointwise_size(data._img_size, data._img_size)   # before the front end launches anything
         batch = data.get_objects() if hasattr(data, "get_objects") else data
@@ -140,8 +186,7 @@ class GenPose2:
                     raise ValueError(f"prev_pose of frame {f} must be ({offsets[f + 1] - offsets[f]},4,4), "
                                      f"got {tuple(p.shape)}")
             prev_pose = torch.cat(prev_pose)
-        pose, length = self.inference(batch, prev_pose=prev_pose, tracking=tracking, tracking_T0=tracking_T0)
-        return [(pose[lo:hi], length[lo:hi]) for lo, hi in zip(offsets[:-1], offsets[1:])]
+        return batch, offsets, prev_pose
 
 
 def create_genpose2(score_model_path: Optional[str], energy_model_path: Optional[str] = None,

@@ -38,6 +38,7 @@ class StageOutputs:
     energy: Optional[torch.Tensor] = None
     aggregated: Optional[torch.Tensor] = None
     length: Optional[torch.Tensor] = None
+    modes: Optional[aggregate.PoseModes] = None   # run(max_modes > 0): every rotation cluster per object
 
 
 class EvaluationPipeline:
@@ -70,12 +71,18 @@ class EvaluationPipeline:
         return s.dino_layers({"roi_rgb": batch["roi_rgb"]})
 
     def run(self, batch: Dict[str, torch.Tensor], init_x: Optional[torch.Tensor] = None, T0: Optional[float] = None,
-            energy_T: Optional[float] = 1e-5) -> StageOutputs:
+            energy_T: Optional[float] = 1e-5, max_modes: int = 0, prev_rot: Optional[torch.Tensor] = None,
+            follow_prev: bool = False) -> StageOutputs:
         """One batch through the stages. The energy network's point encoder depends only on the
         points, so it runs on a side stream concurrently with the score sampler (started after the
         score encoder, whose kernels want the whole chip) and is joined before the energy evaluation.
         ``init_x`` (B,9) and ``T0`` are pred_func's warm start and start time (default: the prior at
-        cfg.T0); ``energy_T`` is get_energy's T (None draws the per-object times, as runners/infer.py does)."""
+        cfg.T0); ``energy_T`` is get_energy's T (None draws the per-object times, as runners/infer.py does).
+
+        ``max_modes`` > 0 (up to 8) replaces the aggregation launch by ``gp_rank_aggregate_modes`` and fills
+        ``modes`` as well (``aggregate.PoseModes``; ``aggregated`` keeps its bits); ``prev_rot`` (B,3,3) gives
+        ``modes.nearest``. With ``follow_prev`` and a ``prev_rot``, ``aggregated`` takes each object's rotation
+        from its nearest slot before the size stage runs (``modes.aggregated`` stays the reference's)."""
         cfg = self.cfg
         data = dict(batch)
         edata = None
@@ -117,9 +124,18 @@ class EvaluationPipeline:
                                                       extract_feature=False)
         energy = out.energy if out.energy is not None else torch.ones(*pred_pose.shape[:2], 2,
                                                                       device=pred_pose.device)
-        out.aggregated = aggregate.aggregate_pose(pred_pose, energy, cfg.retain_ratio, cfg.clustering,
+        if max_modes:   # the same one launch, with every rotation cluster beside the aggregate
+            out.modes = aggregate.aggregate_modes(pred_pose, energy, cfg.retain_ratio, cfg.clustering,
                                                   cfg.clustering_eps, cfg.clustering_minpts,
-                                                  retain_num=int(cfg.eval_repeat_num * cfg.retain_ratio))
+                                                  retain_num=int(cfg.eval_repeat_num * cfg.retain_ratio),
+                                                  max_modes=max_modes, prev_rot=prev_rot)
+            out.aggregated = out.modes.aggregated
+            if follow_prev and prev_rot is not None:
+                out.aggregated = out.modes.follow(out.aggregated)
+        else:
+            out.aggregated = aggregate.aggregate_pose(pred_pose, energy, cfg.retain_ratio, cfg.clustering,
+                                                      cfg.clustering_eps, cfg.clustering_minpts,
+                                                      retain_num=int(cfg.eval_repeat_num * cfg.retain_ratio))
         if self.scale_agent is not None:
             sdata = {"pts_feat": out.pts_feat, "rgb_feat": None,
                      "axes": out.aggregated[:, :3, :3].contiguous()}

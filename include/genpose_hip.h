@@ -747,6 +747,28 @@ int gp_rank_aggregate(const float *poses, const float *energy, int b, int k, int
                       int clustering, float eps, int min_samples, float *aggregated,
                       float *sorted_pose, float *sorted_energy, hipStream_t stream);
 
+/* Pose hypotheses: gp_rank_aggregate's arguments and outputs (the same bits), and in the same one
+ * launch every DBSCAN cluster of the retained rotations instead of the largest alone. max_modes M
+ * is 1..8; prev_rot (b,3,3) may be NULL. With L the number of clusters (0 when clustering == 0),
+ * the clusters fill slots in descending member count, ties to the lower label, so slot 0 is the
+ * cluster gp_rank_aggregate averages; filled = max(1, min(L, M)); with L = 0 slot 0's members are
+ * the whole retained set; slots >= filled are zeros.
+ *   mode_pose   (b,M,4,4) f32  R of the members' quaternion average (slot 0: aggregated's R, bit for
+ *                              bit), t = mean of the members' own translations
+ *   mode_count  (b,M) i32      members
+ *   mode_energy (b,M) f32      mean rotation energy of the members
+ *   mode_spread (b,M) f32      mean 1 - <q_r, q_mode>^2 over the members (the unit of eps)
+ *   n_clusters  (b)   i32      L, not capped by M
+ *   noise_count (b)   i32      retained rotations DBSCAN labelled noise (0 when clustering == 0)
+ *   nearest     (b)   i32      filled slot maximising <q_m, q_prev>^2, q_prev from prev_rot's first
+ *                              two columns (ties to the lower slot); -1 when prev_rot is NULL */
+int gp_rank_aggregate_modes(const float *poses, const float *energy, int b, int k, int retain,
+                            int clustering, float eps, int min_samples, int max_modes,
+                            const float *prev_rot, float *aggregated, float *sorted_pose,
+                            float *sorted_energy, float *mode_pose, int *mode_count,
+                            float *mode_energy, float *mode_spread, int *n_clusters,
+                            int *noise_count, int *nearest, hipStream_t stream);
+
 /* ===================================================================== stage glue
  * process_batch's pts_center (datasets_omni6dpose.py:746-752): out (b,3) = mean over n of
  * pts (b,n,c)[:, :, :3], c >= 3. */
