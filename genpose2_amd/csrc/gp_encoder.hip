@@ -1,21 +1,32 @@
 // PointNet++ MSG set-abstraction encoder for gfx950 (Pointnet2ClsMSG(0), Light config:
-// networks/pts_encoder/pointnet2.py:77-89, 211-252; SA module pointnet2_modules.py:19-124).
+// networks/pts_encoder/pointnet2.py:77-89, 211-252; SA module pointnet2_modules.py:19-124), and the
+// per-level entries the fused pointwise encoder drives (gp_sa_level, gp_sa_level_geom).
 //
-// The reference materialises every grouped tensor (B, 3+C, M, ns) in HBM (group_points_gpu.cu)
-// and runs each 1x1 conv + BN + ReLU as a separate cuDNN call, then max-pools. Here one kernel
-// per (level, branch) does gather -> 2-3 BN-folded layers -> ReLU -> max-pool with the grouped
-// tile never leaving the CU:
-//   * grouped rows are MFMA columns (16 per column tile), output channels are MFMA rows, so
-//     the weights are the streamed A operand (packed once by genpose2_amd/pack.py into the
-//     exact per-lane fragment order: one 1 KiB coalesced load feeds 4 MFMAs per column tile);
-//   * layer-0 B fragments are gathered straight from the previous level's point-major
-//     features (one float4 = 4 channels of one neighbour per lane) with the relative xyz as the
-//     last k-group (input channels are permuted [feats | xyz | pad] so feature float4s align);
-//   * inter-layer activations live in LDS in the MFMA accumulator's native layout, so a layer
-//     writes and the next reads 1 KiB per wave-instruction, linear and conflict-free;
-//   * the max over nsample is taken on the accumulators with 16-lane shuffles.
-// Exact f32 MFMA (v_mfma_f32_16x16x4_f32): no precision is traded.
+// The reference materialises every grouped tensor (B, 3+C, M, ns) in HBM (group_points_gpu.cu) and runs
+// each 1x1 conv + BN + ReLU as a separate cuDNN call, then max-pools. Here the grouped tile never leaves
+// the CU, and layer 0 of every branch is taken once per input point instead of once per grouped column:
+// Q[p] = W0 [f_p | x_p] + b0, so that h0(column) = relu(Q[nbr] - W0_xyz . x_centroid). Per level:
+//   * ball query for both radii (gp_geometry.hip), unless the geometry was computed beforehand;
+//   * layer-0 projection Q: proj_xyz_kernel (level 0 without point features, fp32 fma chains),
+//     proj_feat_kernel (level 0 with point features, exact fp32 MFMA), tok_split_gemm_kernel<2>
+//     (levels 1-3, split-f16) or sa_pair_kernel (levels 1-3, exact fp32 MFMA);
+//   * levels 0-1, sa_narrow_kernel: a wave per centroid, layers 1-2 and the max-pool in registers, each
+//     branch in exact fp32 MFMA (NarrowF32) or split-f16 (NarrowSplit); the FPS levels that follow ride
+//     along as extra workgroups;
+//   * levels 2-3, sa_split_kernel: split-f16 layers 1-2 through LDS planes, 8 waves per workgroup;
+//   * GroupAll, tok_split_gemm_kernel<0> and <1>: two split-f16 token GEMMs, the second max-pools;
+//   * sa_pair_kernel: levels 2-3 and GroupAll in exact fp32 MFMA (v_mfma_f32_16x16x4_f32).
+// Split-f16 (v_mfma_f32_16x16x32_f16, three products of hi/lo planes, fp32 accumulation, power-of-two
+// scales per column and per layer) is the default wherever the packed table carries a layer's planes
+// (pack.pack_encoder): level 0's 32-wide branch, levels 1-3, GroupAll. A table without planes
+// (arith="f32") takes the exact fp32 MFMA form of every kernel: no precision is traded on that path.
+//
+// Layouts the MFMA kernels share: grouped rows are MFMA columns (16 per column tile), output channels are
+// MFMA rows, the weights are the A operand (packed once by genpose2_amd/pack.py into the exact per-lane
+// fragment order); activations between layers stay in the accumulator's native layout, in registers
+// (narrow levels) or LDS; the max over nsample is taken on the accumulators with 16-lane reductions.
 #include <algorithm>
+#include <type_traits>
 
 #include "gp_common.h"
 #include "gp_fps.h"
@@ -42,55 +53,48 @@ struct SAArgs {
     int buf1_off;                     // float4 offset of the second LDS buffer
     int tag;                          // level * 2 + branch (tuning traces)
     // layer 0 by per-point projection (levels 0-3): h0(c, s) = relu(Q[nbr] - W0_xyz . x_c), where
-    // Q[p] = W0_feat . f_p + W0_xyz . x_p + b0 was computed once per point by proj_kernel
+    // Q[p] = W0_feat . f_p + W0_xyz . x_p + b0 was computed once per point by the level's projection launch
     const float* qin;                 // (B, n_prev, q_stride) or null -> layer 0 by MFMA
     int q_stride, q_off;
-    float* proj_out;                  // proj_kernel: Q output (B, n_prev, q_stride) at q_off
+    float* proj_out;                  // projection launch (one layer, no pooling): Q output (B, n_prev, q_stride) at q_off
 };
 
-// Per-wave layer timestamps for tuning builds only (make EXTRA=-DSA_TRACE; scripts/sa_trace.py).
+constexpr int SA_THREADS = 256;   // fp32 pair and narrow kernels: 4 waves per workgroup
+constexpr int SPLIT_WV = 8;       // split-f16 levels 2-3: 8 waves per workgroup
+
+// Per-wave timestamps for tuning builds only (make EXTRA=-DSA_TRACE): buffer, selector, mark and host entry
+// gp_debug_<name> (select a tag and clear, or read back) for kernels of WAVES waves per workgroup.
+//   sa_trace (sa_pair_kernel, scripts/sa_trace.py): marks 0 start, 2L+1 after layer L, 2L+2 after its barrier;
+//   split_trace (sa_split_kernel, scripts/split_trace.py): marks 0 start, 1 staged + barrier, 2 layer-0 gather
+//   + barrier, 3 layer-1 stream done, 4 column-max barrier, 5 layer-1 planes written, 6 layer-2 barrier, 7 end
 #ifdef SA_TRACE
-__device__ unsigned long long g_sa_trace[8192 * 4 * 8];
-__device__ int g_sa_trace_sel = -1;
-#define SA_MARK(k)                                                                                         \
-    do {                                                                                                   \
-        const int wg_ = blockIdx.y * gridDim.x + blockIdx.x;                                               \
-        if (a.tag == g_sa_trace_sel && (threadIdx.x & 63) == 0 && wg_ < 8192)                              \
-            g_sa_trace[(wg_ * 4 + (threadIdx.x >> 6)) * 8 + (k)] = __builtin_amdgcn_s_memtime();          \
-    } while (0)
-extern "C" int gp_debug_sa_trace(int sel, unsigned long long* host) {
-    if (host) return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_sa_trace), sizeof(g_sa_trace)) == hipSuccess ? 0 : -1;
-    void* ptr = nullptr;
-    if (hipGetSymbolAddress(&ptr, HIP_SYMBOL(g_sa_trace)) != hipSuccess || hipMemset(ptr, 0, sizeof(g_sa_trace)) != hipSuccess)
-        return -1;
-    return hipMemcpyToSymbol(HIP_SYMBOL(g_sa_trace_sel), &sel, sizeof(int)) == hipSuccess ? 0 : -1;
-}
-// split-f16 levels (8 waves per workgroup): marks 0 start, 1 staged + barrier, 2 layer-0 gather + barrier,
-// 3 layer-1 stream done, 4 column-max barrier, 5 layer-1 planes written, 6 layer-2 barrier, 7 end
-__device__ unsigned long long g_split_trace[8192 * 8 * 8];
-__device__ int g_split_trace_sel = -1;
-#define SPLIT_MARK(a, k)                                                                                   \
-    do {                                                                                                   \
-        const int wg_ = blockIdx.y * gridDim.x + blockIdx.x;                                               \
-        if ((a).tag == g_split_trace_sel && (threadIdx.x & 63) == 0 && wg_ < 8192)                         \
-            g_split_trace[(wg_ * 8 + (threadIdx.x >> 6)) * 8 + (k)] = __builtin_amdgcn_s_memtime();       \
-    } while (0)
-extern "C" int gp_debug_split_trace(int sel, unsigned long long* host) {
-    if (host) return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_split_trace), sizeof(g_split_trace)) == hipSuccess ? 0 : -1;
-    void* ptr = nullptr;
-    if (hipGetSymbolAddress(&ptr, HIP_SYMBOL(g_split_trace)) != hipSuccess || hipMemset(ptr, 0, sizeof(g_split_trace)) != hipSuccess)
-        return -1;
-    return hipMemcpyToSymbol(HIP_SYMBOL(g_split_trace_sel), &sel, sizeof(int)) == hipSuccess ? 0 : -1;
-}
+#define GP_WAVE_TRACE(name, WAVES)                                                                                   \
+    __device__ unsigned long long g_##name[8192 * WAVES * 8];                                                        \
+    __device__ int g_##name##_sel = -1;                                                                              \
+    __device__ __forceinline__ void name##_mark(int tag, int k) {                                                    \
+        const int wg = blockIdx.y * gridDim.x + blockIdx.x;                                                          \
+        if (tag == g_##name##_sel && (threadIdx.x & 63) == 0 && wg < 8192)                                           \
+            g_##name[(wg * WAVES + (threadIdx.x >> 6)) * 8 + k] = __builtin_amdgcn_s_memtime();                      \
+    }                                                                                                                \
+    extern "C" int gp_debug_##name(int sel, unsigned long long* host) {                                              \
+        if (host) return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_##name), sizeof(g_##name)) == hipSuccess ? 0 : -1;   \
+        void* ptr = nullptr;                                                                                         \
+        if (hipGetSymbolAddress(&ptr, HIP_SYMBOL(g_##name)) != hipSuccess ||                                         \
+            hipMemset(ptr, 0, sizeof(g_##name)) != hipSuccess)                                                       \
+            return -1;                                                                                               \
+        return hipMemcpyToSymbol(HIP_SYMBOL(g_##name##_sel), &sel, sizeof(int)) == hipSuccess ? 0 : -1;              \
+    }
+GP_WAVE_TRACE(sa_trace, (SA_THREADS / 64))
+GP_WAVE_TRACE(split_trace, SPLIT_WV)
+#undef GP_WAVE_TRACE
+#define SA_MARK(k) sa_trace_mark(a.tag, k)
+#define SPLIT_MARK(a, k) split_trace_mark((a).tag, k)
 #else
 #define SA_MARK(k) ((void)0)
 #define SPLIT_MARK(a, k) ((void)0)
 #endif
 
-constexpr int SA_THREADS = 256;
-#ifndef SA_RING
-#define SA_RING 2        // k-groups of operands in flight + 1
-#endif
+constexpr int SA_RING = 2;   // k-groups of operands in flight + 1
 
 // One layer for the CTW column tiles [cbase, cbase+CTW) of this wave and the output tiles
 // wt*TC, wt*TC + WT*TC, ... (WT = waves sharing the columns). Layers narrower than 4*TC output
@@ -386,7 +390,6 @@ __global__ __launch_bounds__(SA_THREADS, 2) void sa_pair_kernel(SAArgs a0, SAArg
 // Weights carry a per-layer exponent (pack.pack_encoder). Wave w owns output chunks w, w+8, ...: the
 // two waves sharing a SIMD (w, w+4) split a level-3 branch-1 layer 1's 12 chunks 2 + 1.
 // 64 columns per workgroup: every weight fragment streamed from L2 feeds 4 column tiles x 3 MFMAs.
-constexpr int SPLIT_WV = 8;
 
 struct SplitArgs {
     int n_prev, m, ns, cols;          // cols = m * ns, a multiple of the workgroup's 16*CT columns
@@ -695,18 +698,8 @@ __global__ __launch_bounds__(SPLIT_WV * 64) __attribute__((amdgpu_waves_per_eu(2
 // streamed from L2 then feeds 6 column tiles (1.69 -> 1.31 ms at B=256). Level 2 keeps 4 tiles, two
 // workgroups per CU whose gather and barrier phases overlap each other's streams (8 tiles: 0.87 ->
 // 1.40 ms).
-#ifndef SPLIT_CT2
-#define SPLIT_CT2 4
-#endif
-#ifndef SPLIT_CT3
-#define SPLIT_CT3 6
-#endif
-#ifndef SPLIT_D2
-#define SPLIT_D2 2
-#endif
-#ifndef SPLIT_D3
-#define SPLIT_D3 2
-#endif
+constexpr int SPLIT_CT2 = 4, SPLIT_CT3 = 6;
+constexpr int SPLIT_D2 = 2, SPLIT_D3 = 2;
 
 template <int CT, int KC0, int OC1>
 static size_t sa_split_lds() {
@@ -733,7 +726,7 @@ struct NarrowArgs {
     int m, ns, nobj;
     float* out;            // (B, m, c_out_total)
     int c_out_total, out_off;
-    const float* w1h;      // split-f16 planes of layers 1 / 2 (sa_narrow_split_kernel) and their exponents
+    const float* w1h;      // split-f16 planes of layers 1 / 2 (NarrowSplit) and their exponents
     const float* w2h;
     int ew1, ew2;
 };
@@ -788,18 +781,60 @@ __device__ __forceinline__ void narrow_fetch(const NarrowArgs& a, int task, cons
     }
 }
 
-template <int KG1, int NT1, int NT2, int SPAN>
+// The arithmetic of a narrow branch's layers 1-2, and with it the LDS layout of its weights. KG1 16-deep
+// k-groups of layer 0's output, NT1 and NT2 output tiles of layers 1 and 2, SPAN column tiles per centroid,
+// NA1 and NA2 16-byte weight fragments of layers 1 and 2 in LDS.
+// Exact fp32 MFMA (v_mfma_f32_16x16x4_f32): the accumulator tile g of layer 1 is k-group g of layer 2's B
+// operand as is.
+template <int KG1_, int NT1_, int NT2_, int SPAN_>
+struct NarrowF32 {
+    static constexpr bool SPLIT = false;
+    static constexpr int KG1 = KG1_, NT1 = NT1_, NT2 = NT2_, SPAN = SPAN_, KG2 = NT1;
+    static constexpr int NA1 = NT1 * KG1 * 64, NA2 = NT2 * KG2 * 64;
+    typedef f32x4 Frag;
+};
+// Split-f16 MFMA (v_mfma_f32_16x16x32_f16, three products of hi/lo planes, fp32 accumulation, as
+// sa_split_kernel) and per-column power-of-two activation scaling. A column's values sit in the four lanes
+// (q, n) of its column index n, so the column maximum is a 4-lane max of registers: layer 0's from the
+// gathered projection, layer 1's from its accumulators. The accumulator tiles 2c, 2c+1 of one layer are
+// chunk c of the next layer's B operand as is, so the activations never leave registers. KC0 = 32-deep
+// chunks of layer 0's output (its width / 32).
+template <int KC0_, int NT1_, int NT2_, int SPAN_>
+struct NarrowSplit {
+    static constexpr bool SPLIT = true;
+    static constexpr int KC0 = KC0_, KG1 = 2 * KC0, NT1 = NT1_, NT2 = NT2_, SPAN = SPAN_, KC1 = NT1 / 2;
+    static_assert(NT1 % 2 == 0, "layer-1 tiles pair into 32-deep chunks");
+    static constexpr int NA1 = NT1 * KC0 * 2 * 64, NA2 = NT2 * KC1 * 2 * 64;
+    typedef f16x8 Frag;
+};
+
+// Dynamic LDS of a narrow branch: [layer-1 fragments | layer-2 fragments | W0_xyz rows | bias 1 | bias 2].
+template <class Math>
+constexpr size_t narrow_lds_bytes() {
+    return 16 * ((size_t)Math::NA1 + Math::NA2 + Math::KG1 * 16) + sizeof(float) * 16 * (Math::NT1 + Math::NT2);
+}
+
+// The wave program of a narrow branch: stage the weights, then this wave's centroids, one at a time. The
+// two arithmetics' staging and column-tile steps stand here under `if constexpr`, not in functions of
+// their policies: a callee is simplified on its own before it is inlined, which moved the schedule and
+// cost every instantiation 1-2 VGPRs.
+template <class Math>
 __device__ __forceinline__ void narrow_branch(const NarrowArgs& a, f32x4* lds) {
-    constexpr int KG2 = NT1;
-    constexpr int NA1 = NT1 * KG1 * 64, NA2 = NT2 * KG2 * 64;
-    f32x4* sA1 = lds;
-    f32x4* sA2 = sA1 + NA1;
-    f32x4* sW0x = sA2 + NA2;              // [KG1*16] (wx, wy, wz, 0) per layer-0 output channel
+    constexpr int KG1 = Math::KG1, NT1 = Math::NT1, NT2 = Math::NT2, SPAN = Math::SPAN;
+    typedef typename Math::Frag Frag;
+    Frag* sA1 = reinterpret_cast<Frag*>(lds);
+    Frag* sA2 = sA1 + Math::NA1;
+    f32x4* sW0x = reinterpret_cast<f32x4*>(sA2 + Math::NA2);   // [KG1*16] (wx, wy, wz, 0) per layer-0 output channel
     float* sB1 = reinterpret_cast<float*>(sW0x + KG1 * 16);
     float* sB2 = sB1 + NT1 * 16;
     const int tid = threadIdx.x;
-    for (int i = tid; i < NA1; i += SA_THREADS) sA1[i] = ld4(a.w1 + (size_t)i * 4);
-    for (int i = tid; i < NA2; i += SA_THREADS) sA2[i] = ld4(a.w2 + (size_t)i * 4);
+    if constexpr (Math::SPLIT) {
+        for (int i = tid; i < Math::NA1; i += SA_THREADS) sA1[i] = __builtin_bit_cast(f16x8, ld4(a.w1h + (size_t)i * 4));
+        for (int i = tid; i < Math::NA2; i += SA_THREADS) sA2[i] = __builtin_bit_cast(f16x8, ld4(a.w2h + (size_t)i * 4));
+    } else {
+        for (int i = tid; i < Math::NA1; i += SA_THREADS) sA1[i] = ld4(a.w1 + (size_t)i * 4);
+        for (int i = tid; i < Math::NA2; i += SA_THREADS) sA2[i] = ld4(a.w2 + (size_t)i * 4);
+    }
     for (int ch = tid; ch < KG1 * 16; ch += SA_THREADS)   // packed layer-0 fragment of channel ch, q = 0
         sW0x[ch] = ld4(a.w0 + ((size_t)((ch >> 4) * a.kg0 + a.gx) * 64 + (ch & 15)) * 4);
     for (int i = tid; i < NT1 * 16; i += SA_THREADS) sB1[i] = a.b1[i];
@@ -829,164 +864,108 @@ __device__ __forceinline__ void narrow_branch(const NarrowArgs& a, f32x4* lds) {
 #pragma unroll
         for (int ct = 0; ct < SPAN; ++ct) {
             f32x4 bf[KG1];
+            if constexpr (!Math::SPLIT) {
+                constexpr int KG2 = Math::KG2;
 #pragma unroll
-            for (int g = 0; g < KG1; ++g) {
-                float r[4];
+                for (int g = 0; g < KG1; ++g) {
+                    float r[4];
 #pragma unroll
-                for (int j = 0; j < 4; ++j) r[j] = relu1(fsub(cur.q[ct][g][j], cw[g][j]));
-                bf[g] = f32x4{r[0], r[1], r[2], r[3]};
-            }
-            f32x4 acc1[NT1];
-#pragma unroll
-            for (int t = 0; t < NT1; ++t) acc1[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int g = 0; g < KG1; ++g) {
-                f32x4 af[NT1];
-#pragma unroll
-                for (int t = 0; t < NT1; ++t) af[t] = sA1[(t * KG1 + g) * 64 + lane];
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-#pragma unroll
-                    for (int t = 0; t < NT1; ++t) acc1[t] = mfma4(af[t][j], bf[g][j], acc1[t]);
-                __builtin_amdgcn_sched_barrier(0);   // bound the live A fragments to one k-group
-            }
-#pragma unroll
-            for (int t = 0; t < NT1; ++t) acc1[t] = relu4(acc1[t] + ld4(&sB1[16 * t + 4 * q]));
-            f32x4 acc2[NT2];
-#pragma unroll
-            for (int t = 0; t < NT2; ++t) acc2[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int g = 0; g < KG2; ++g) {
-                f32x4 af[NT2];
-#pragma unroll
-                for (int t = 0; t < NT2; ++t) af[t] = sA2[(t * KG2 + g) * 64 + lane];
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-#pragma unroll
-                    for (int t = 0; t < NT2; ++t) acc2[t] = mfma4(af[t][j], acc1[g][j], acc2[t]);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-#pragma unroll
-            for (int t = 0; t < NT2; ++t) rmax[t] = vmax4(rmax[t], acc2[t]);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        float* o = a.out + (size_t)task * a.c_out_total + a.out_off + 4 * q;
-#pragma unroll
-        for (int t = 0; t < NT2; ++t) {
-            const int j = nn >> 2;   // row16_max_scatter4 leaves channel 16 t + 4 q + j in this quad
-            const float r = relu1(row16_max_scatter4(rmax[t], nn) + sB2[16 * t + 4 * q + j]);
-            if ((nn & 3) == 0) o[16 * t + j] = r;
-        }
-        cur = nxt;
-    }
-}
-
-// Narrow level with layers 1-2 as split-f16 MFMA (v_mfma_f32_16x16x32_f16, three products of hi/lo
-// planes, fp32 accumulation, as sa_split_kernel) and per-column power-of-two activation scaling. A
-// column's values sit in the four lanes (q, n) of its column index n, so the column maximum is a 4-lane
-// max of registers: layer 0's from the gathered projection, layer 1's from its accumulators. The
-// accumulator tiles 2c, 2c+1 of one layer are chunk c of the next layer's B operand as is, so the
-// activations never leave registers. KC0 = 32-deep chunks of layer 0's output (its width / 32).
-template <int KC0, int NT1, int NT2, int SPAN>
-__device__ __forceinline__ void narrow_branch_split(const NarrowArgs& a, f32x4* lds) {
-    constexpr int KG1 = 2 * KC0, KC1 = NT1 / 2;
-    static_assert(NT1 % 2 == 0, "layer-1 tiles pair into 32-deep chunks");
-    constexpr int NA1 = NT1 * KC0 * 2 * 64, NA2 = NT2 * KC1 * 2 * 64;   // f16x8 fragments
-    f16x8* sA1 = reinterpret_cast<f16x8*>(lds);
-    f16x8* sA2 = sA1 + NA1;
-    f32x4* sW0x = reinterpret_cast<f32x4*>(sA2 + NA2);
-    float* sB1 = reinterpret_cast<float*>(sW0x + KG1 * 16);
-    float* sB2 = sB1 + NT1 * 16;
-    const int tid = threadIdx.x;
-    for (int i = tid; i < NA1; i += SA_THREADS) sA1[i] = __builtin_bit_cast(f16x8, ld4(a.w1h + (size_t)i * 4));
-    for (int i = tid; i < NA2; i += SA_THREADS) sA2[i] = __builtin_bit_cast(f16x8, ld4(a.w2h + (size_t)i * 4));
-    for (int ch = tid; ch < KG1 * 16; ch += SA_THREADS)
-        sW0x[ch] = ld4(a.w0 + ((size_t)((ch >> 4) * a.kg0 + a.gx) * 64 + (ch & 15)) * 4);
-    for (int i = tid; i < NT1 * 16; i += SA_THREADS) sB1[i] = a.b1[i];
-    for (int i = tid; i < NT2 * 16; i += SA_THREADS) sB2[i] = a.b2[i];
-    __syncthreads();
-    const int lane = tid & 63, q = lane >> 4, nn = lane & 15;
-    const int nw = gridDim.x * (SA_THREADS / 64);
-    const int total = a.nobj * a.m;
-    int task = blockIdx.x * (SA_THREADS / 64) + (tid >> 6);
-    if (task >= total) return;
-    int pn[SPAN];
-    NarrowGather<SPAN, KG1> cur, nxt;
-    f32x4 cwv[KG1];
-    narrow_nbr<SPAN>(a, task, nn, pn);
-    narrow_fetch<SPAN, KG1>(a, task, pn, q, cur);
-    if (task + nw < total) narrow_nbr<SPAN>(a, task + nw, nn, pn);
-    for (; task < total; task += nw) {
-        if (task + nw < total) {
-            narrow_fetch<SPAN, KG1>(a, task + nw, pn, q, nxt);
-            if (task + 2 * nw < total) narrow_nbr<SPAN>(a, task + 2 * nw, nn, pn);
-        }
-        const float cx = cur.cx, cy = cur.cy, cz = cur.cz;
-        f32x4 rmax[NT2];
-#pragma unroll
-        for (int t = 0; t < NT2; ++t) rmax[t] = f32x4{NEG_BIG, NEG_BIG, NEG_BIG, NEG_BIG};   // pre-bias maxima
-        const f32x4* cw = narrow_centroid_term<KG1>(sW0x, q, cx, cy, cz, cwv);
-#pragma unroll
-        for (int ct = 0; ct < SPAN; ++ct) {
-            f32x4 bf[KG1];
-            float mx = 0.f;
-#pragma unroll
-            for (int g = 0; g < KG1; ++g) {
-                float r[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    r[j] = relu1(fsub(cur.q[ct][g][j], cw[g][j]));
-                    mx = fmax2(mx, r[j]);
+                    for (int j = 0; j < 4; ++j) r[j] = relu1(fsub(cur.q[ct][g][j], cw[g][j]));
+                    bf[g] = f32x4{r[0], r[1], r[2], r[3]};
                 }
-                bf[g] = f32x4{r[0], r[1], r[2], r[3]};
-            }
-            // layer 0 -> chunk planes at the column's scale
-            const int E0 = col_exponent(rows_max(mx));
-            f16x8 h0[KC0], l0[KC0];
+                f32x4 acc1[NT1];
 #pragma unroll
-            for (int c = 0; c < KC0; ++c) split_pair(bf[2 * c], bf[2 * c + 1], exp2i(14 - E0), h0[c], l0[c]);
-            f32x4 acc1[NT1];
+                for (int t = 0; t < NT1; ++t) acc1[t] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-            for (int t = 0; t < NT1; ++t) acc1[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+                for (int g = 0; g < KG1; ++g) {
+                    f32x4 af[NT1];
 #pragma unroll
-            for (int c = 0; c < KC0; ++c) {
+                    for (int t = 0; t < NT1; ++t) af[t] = sA1[(t * KG1 + g) * 64 + lane];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+#pragma unroll
+                        for (int t = 0; t < NT1; ++t) acc1[t] = mfma4(af[t][j], bf[g][j], acc1[t]);
+                    __builtin_amdgcn_sched_barrier(0);   // bound the live A fragments to one k-group
+                }
+#pragma unroll
+                for (int t = 0; t < NT1; ++t) acc1[t] = relu4(acc1[t] + ld4(&sB1[16 * t + 4 * q]));
+                f32x4 acc2[NT2];
+#pragma unroll
+                for (int t = 0; t < NT2; ++t) acc2[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int g = 0; g < KG2; ++g) {
+                    f32x4 af[NT2];
+#pragma unroll
+                    for (int t = 0; t < NT2; ++t) af[t] = sA2[(t * KG2 + g) * 64 + lane];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+#pragma unroll
+                        for (int t = 0; t < NT2; ++t) acc2[t] = mfma4(af[t][j], acc1[g][j], acc2[t]);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+#pragma unroll
+                for (int t = 0; t < NT2; ++t) rmax[t] = vmax4(rmax[t], acc2[t]);
+            } else {
+                constexpr int KC0 = Math::KC0, KC1 = Math::KC1;
+                float mx = 0.f;
+#pragma unroll
+                for (int g = 0; g < KG1; ++g) {
+                    float r[4];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        r[j] = relu1(fsub(cur.q[ct][g][j], cw[g][j]));
+                        mx = fmax2(mx, r[j]);
+                    }
+                    bf[g] = f32x4{r[0], r[1], r[2], r[3]};
+                }
+                // layer 0 -> chunk planes at the column's scale
+                const int E0 = col_exponent(rows_max(mx));
+                f16x8 h0[KC0], l0[KC0];
+#pragma unroll
+                for (int c = 0; c < KC0; ++c) split_pair(bf[2 * c], bf[2 * c + 1], exp2i(14 - E0), h0[c], l0[c]);
+                f32x4 acc1[NT1];
+#pragma unroll
+                for (int t = 0; t < NT1; ++t) acc1[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int c = 0; c < KC0; ++c) {
+#pragma unroll
+                    for (int t = 0; t < NT1; ++t) {
+                        const f16x8 ah = sA1[((t * KC0 + c) * 2 + 0) * 64 + lane];
+                        const f16x8 al = sA1[((t * KC0 + c) * 2 + 1) * 64 + lane];
+                        acc1[t] = mfma_h(al, h0[c], acc1[t]);
+                        acc1[t] = mfma_h(ah, l0[c], acc1[t]);
+                        acc1[t] = mfma_h(ah, h0[c], acc1[t]);
+                    }
+                }
+                const float u0 = exp2i(E0 - 14 - a.ew1);
+                float m1 = 0.f;
 #pragma unroll
                 for (int t = 0; t < NT1; ++t) {
-                    const f16x8 ah = sA1[((t * KC0 + c) * 2 + 0) * 64 + lane];
-                    const f16x8 al = sA1[((t * KC0 + c) * 2 + 1) * 64 + lane];
-                    acc1[t] = mfma_h(al, h0[c], acc1[t]);
-                    acc1[t] = mfma_h(ah, l0[c], acc1[t]);
-                    acc1[t] = mfma_h(ah, h0[c], acc1[t]);
+                    acc1[t] = relu4(acc1[t] * u0 + ld4(&sB1[16 * t + 4 * q]));
+                    m1 = fmax2(m1, max4(acc1[t]));
                 }
-            }
-            const float u0 = exp2i(E0 - 14 - a.ew1);
-            float m1 = 0.f;
+                const int E1 = col_exponent(rows_max(m1));
+                f16x8 h1[KC1], l1[KC1];
 #pragma unroll
-            for (int t = 0; t < NT1; ++t) {
-                acc1[t] = relu4(acc1[t] * u0 + ld4(&sB1[16 * t + 4 * q]));
-                m1 = fmax2(m1, max4(acc1[t]));
-            }
-            const int E1 = col_exponent(rows_max(m1));
-            f16x8 h1[KC1], l1[KC1];
+                for (int c = 0; c < KC1; ++c) split_pair(acc1[2 * c], acc1[2 * c + 1], exp2i(14 - E1), h1[c], l1[c]);
+                f32x4 acc2[NT2];
 #pragma unroll
-            for (int c = 0; c < KC1; ++c) split_pair(acc1[2 * c], acc1[2 * c + 1], exp2i(14 - E1), h1[c], l1[c]);
-            f32x4 acc2[NT2];
+                for (int t = 0; t < NT2; ++t) acc2[t] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-            for (int t = 0; t < NT2; ++t) acc2[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+                for (int c = 0; c < KC1; ++c) {
 #pragma unroll
-            for (int c = 0; c < KC1; ++c) {
-#pragma unroll
-                for (int t = 0; t < NT2; ++t) {
-                    const f16x8 ah = sA2[((t * KC1 + c) * 2 + 0) * 64 + lane];
-                    const f16x8 al = sA2[((t * KC1 + c) * 2 + 1) * 64 + lane];
-                    acc2[t] = mfma_h(al, h1[c], acc2[t]);
-                    acc2[t] = mfma_h(ah, l1[c], acc2[t]);
-                    acc2[t] = mfma_h(ah, h1[c], acc2[t]);
+                    for (int t = 0; t < NT2; ++t) {
+                        const f16x8 ah = sA2[((t * KC1 + c) * 2 + 0) * 64 + lane];
+                        const f16x8 al = sA2[((t * KC1 + c) * 2 + 1) * 64 + lane];
+                        acc2[t] = mfma_h(al, h1[c], acc2[t]);
+                        acc2[t] = mfma_h(ah, l1[c], acc2[t]);
+                        acc2[t] = mfma_h(ah, h1[c], acc2[t]);
+                    }
                 }
-            }
-            const float u1 = exp2i(E1 - 14 - a.ew2);
+                const float u1 = exp2i(E1 - 14 - a.ew2);
 #pragma unroll
-            for (int t = 0; t < NT2; ++t) rmax[t] = vmax4(rmax[t], acc2[t] * u1);
+                for (int t = 0; t < NT2; ++t) rmax[t] = vmax4(rmax[t], acc2[t] * u1);
+            }
             __builtin_amdgcn_sched_barrier(0);
         }
         float* o = a.out + (size_t)task * a.c_out_total + a.out_off + 4 * q;
@@ -1045,8 +1024,11 @@ __device__ __forceinline__ void fps_side(const FpsSide& f, char* smem) {
     }
 }
 
-// Both branches of a narrow level in one launch (blockIdx.y = 1 + branch), plus FPS side work.
-template <int KG1a, int NT1a, int NT2a, int SPANa, int KG1b, int NT1b, int NT2b, int SPANb>
+// Both branches of a narrow level in one launch (blockIdx.y = 1 + branch), plus FPS side work. Each branch
+// takes its own arithmetic: level 0 runs its 16-wide branch in exact fp32 (its layer 0 does not fill a
+// 32-deep chunk) beside its 32-wide branch in split-f16 (5x fewer MFMA cycles than fp32 16x16x4), level 1
+// both in split-f16; the exact-fp32 encoder runs both levels as NarrowF32.
+template <class BranchA, class BranchB>
 __global__ __launch_bounds__(SA_THREADS) void sa_narrow_kernel(NarrowArgs a0, NarrowArgs a1, FpsSide f) {
     extern __shared__ __attribute__((aligned(16))) f32x4 lds[];
     // FPS first (blockIdx.y == 0): the dispatcher issues workgroups in linear order, so the
@@ -1054,46 +1036,17 @@ __global__ __launch_bounds__(SA_THREADS) void sa_narrow_kernel(NarrowArgs a0, Na
     if (blockIdx.y == 0)
         fps_side(f, reinterpret_cast<char*>(lds));
     else if (blockIdx.y == 1)
-        narrow_branch<KG1a, NT1a, NT2a, SPANa>(a0, lds);
+        narrow_branch<BranchA>(a0, lds);
     else
-        narrow_branch<KG1b, NT1b, NT2b, SPANb>(a1, lds);
+        narrow_branch<BranchB>(a1, lds);
 }
 
-// Level 1 with split-f16 layers 1-2 (both branches), FPS levels 2-3 beside it.
-template <int KC0a, int NT1a, int NT2a, int SPANa, int KC0b, int NT1b, int NT2b, int SPANb>
-__global__ __launch_bounds__(SA_THREADS) void sa_narrow_split_kernel(NarrowArgs a0, NarrowArgs a1, FpsSide f) {
-    extern __shared__ __attribute__((aligned(16))) f32x4 lds[];
-    if (blockIdx.y == 0)
-        fps_side(f, reinterpret_cast<char*>(lds));
-    else if (blockIdx.y == 1)
-        narrow_branch_split<KC0a, NT1a, NT2a, SPANa>(a0, lds);
-    else
-        narrow_branch_split<KC0b, NT1b, NT2b, SPANb>(a1, lds);
-}
-
-// Level 0: the 16-wide branch in exact fp32 (its layer 0 does not fill a 32-deep chunk), the 32-wide
-// branch with split-f16 layers 1-2 (5x fewer MFMA cycles than fp32 16x16x4), FPS level 1 beside them.
-template <int KG1a, int NT1a, int NT2a, int SPANa, int KC0b, int NT1b, int NT2b, int SPANb>
-__global__ __launch_bounds__(SA_THREADS) void sa_narrow_mixed_kernel(NarrowArgs a0, NarrowArgs a1, FpsSide f) {
-    extern __shared__ __attribute__((aligned(16))) f32x4 lds[];
-#ifdef NARROW_PROBE   // timing probes only (results are wrong): 1 = FPS only, 2 = branch a only, 3 = branch b only
-    if (blockIdx.y != (NARROW_PROBE - 1)) return;
-#endif
-    if (blockIdx.y == 0)
-        fps_side(f, reinterpret_cast<char*>(lds));
-    else if (blockIdx.y == 1)
-        narrow_branch<KG1a, NT1a, NT2a, SPANa>(a0, lds);
-    else
-        narrow_branch_split<KC0b, NT1b, NT2b, SPANb>(a1, lds);
-}
-
-static size_t narrow_split_lds(int kc0, int nt1, int nt2) {
-    return 16 * ((size_t)nt1 * kc0 * 2 * 64 + (size_t)nt2 * (nt1 / 2) * 2 * 64 + (size_t)2 * kc0 * 16) +
-           sizeof(float) * 16 * (nt1 + nt2);
-}
-
-static size_t narrow_lds(int kg1, int nt1, int nt2) {
-    return sizeof(f32x4) * ((size_t)nt1 * kg1 * 64 + (size_t)nt2 * nt1 * 64 + kg1 * 16) + sizeof(float) * 16 * (nt1 + nt2);
+template <class BranchA, class BranchB>
+static int launch_narrow(const NarrowArgs& a0, const NarrowArgs& a1, const FpsSide& fs, hipStream_t st) {
+    const size_t lds = std::max({narrow_lds_bytes<BranchA>(), narrow_lds_bytes<BranchB>(), fps_side_lds(fs)});
+    hipLaunchKernelGGL((sa_narrow_kernel<BranchA, BranchB>), dim3(std::max(512, a0.nobj), 3), dim3(SA_THREADS), lds, st,
+                       a0, a1, fs);
+    return gp_check_launch("sa_narrow_kernel");
 }
 
 // ============================================================================ split-f16 token GEMMs
@@ -1316,9 +1269,6 @@ __global__ __launch_bounds__(TG_THREADS) void tok_split_gemm_kernel(TokArgs a) {
 // pointer and projected its points with the other branch's bias -- the one-off wrong level-0 features
 // behind the round-4 multirank mismatch (scripts/race_probe.py; tests/test_cpu_host.py checks every kernel
 // of the library for vector loads from the argument segment).
-#ifndef PROJ_DIAG
-#define PROJ_DIAG 0
-#endif
 struct ProjXyzArgs {
     const float* xyz;       // (B * n, 3)
     int npts;               // B * n
@@ -1344,21 +1294,9 @@ __global__ __launch_bounds__(256) void proj_xyz_kernel(ProjXyzArgs a) {
         const int ch = c0 + j;
         const f32x4 w = ld4(w0 + ((size_t)(ch >> 4) * 64 + (ch & 15)) * 4);
         float acc = __builtin_fmaf(w.x, x, 0.f);
-#if PROJ_DIAG & 2   // diagnostic: opaque values between the chains, so no packed-FP32 (v_pk_fma_f32) forms
-        asm volatile("" : "+v"(acc));
-#endif
         acc = __builtin_fmaf(w.y, y, acc);
-#if PROJ_DIAG & 2
-        asm volatile("" : "+v"(acc));
-#endif
         acc = __builtin_fmaf(w.z, z, acc);
-#if PROJ_DIAG & 2
-        asm volatile("" : "+v"(acc));
-#endif
         v[j] = acc + b0[ch];
-#if PROJ_DIAG & 2
-        asm volatile("" : "+v"(v[j]));
-#endif
     }
     st4(a.q + (size_t)p * a.q_stride + qoff + 4 * g, f32x4{v[0], v[1], v[2], v[3]});
 }
@@ -1370,12 +1308,8 @@ __global__ __launch_bounds__(256) void proj_xyz_kernel(ProjXyzArgs a) {
 // group last) are kept RING deep in flight. Per
 // accumulator the MFMA sequence is sa_layer's projection pass (k-group g outer, its four k-steps j inner, the same
 // operands): the same bits, where sa_pair_kernel read each row once per branch with one k-group in flight.
-#ifndef PROJ_FEAT_CTW
-#define PROJ_FEAT_CTW 4
-#endif
-#ifndef PROJ_FEAT_RING
-#define PROJ_FEAT_RING 2
-#endif
+constexpr int PROJ_FEAT_CTW = 4;    // column tiles (16 points each) per wave
+constexpr int PROJ_FEAT_RING = 2;   // k-groups of operands in flight + 1
 struct ProjFeatArgs {
     const float* feat;     // (npts, c_prev) point-major
     const float* xyz;      // (npts, 3)
@@ -1560,6 +1494,11 @@ static int launch_pair(SAArgs a0, SAArgs a1, int B, hipStream_t st) {
 // Row of the packed-layer table (pack.pack_encoder, [5][2][3][4]): {fp32 fragments, bias, split
 // planes or -1, split exponent}.
 static inline const int64_t* enc_layer(const int64_t* tab, int l, int br, int i) { return tab + ((l * 2 + br) * 3 + i) * 4; }
+// Layer (l, br, i) carries split-f16 planes; layers i and j of both branches of level l do.
+static inline bool has_split(const int64_t* tab, int l, int br, int i) { return enc_layer(tab, l, br, i)[2] >= 0; }
+static inline bool level_split(const int64_t* tab, int l, int i, int j) {
+    return has_split(tab, l, 0, i) && has_split(tab, l, 0, j) && has_split(tab, l, 1, i) && has_split(tab, l, 1, j);
+}
 
 // Per-call view of the encoder workspace (enc_layout) and the packed layer table.
 // geo: the workspace that holds (or receives) the geometry -- FPS indices, centroids, ball lists -- which
@@ -1705,279 +1644,281 @@ static int run_groupall_split(const EncCtx& c, const float* feat_prev, float* ou
     return gp_check_launch("tok_split_gemm_kernel");
 }
 
-// One SA level l (ball query, per-point layer 0, layers 1-2 + max-pool) over the FPS results already
-// in the workspace. feat_prev (B, n_prev, c_prev) point-major or null (c_prev = 0); out (B, M_l, C_l).
-// side: FPS levels that ride along as extra workgroups of the narrow launches (gp_encoder_forward),
-// or null when the FPS chain ran whole beforehand (gp_encoder_fps).
-static int run_sa_level(const EncCtx& c, int l, int c_prev, const float* feat_prev, float* out, bool side,
-                        hipStream_t st) {
-    const int B = c.B;
-    const float* wbuf = c.wbuf;
-    const int64_t* layer_off = c.tab;
-    const float* xyz_prev = l == 0 ? c.pts : c.nxyz[l - 1];
-    const int n_prev = l == 0 ? c.N : kNpoint[l - 1];
-    int rc = GP_OK;
-    int* b0 = nullptr;
-    int* b1 = nullptr;
+// One call of run_sa_level: level l's inputs, its scratch in the workspace and its output.
+struct SALevel {
+    int l, c_prev, n_prev;
+    const float* xyz_prev;    // (B, n_prev, 3)
+    const float* feat_prev;   // (B, n_prev, c_prev) point-major, or null (c_prev = 0)
+    int* ball[2];             // neighbour lists of the two radii (levels 0-3)
+    float* qbuf;              // per-point layer-0 projection of both branches (levels 0-3)
+    float* out;               // (B, M_l, C_l)
+};
+
+// The per-branch fields that the level kernels' argument structs (SAArgs, NarrowArgs, SplitArgs) share.
+template <class Args>
+static void fill_branch(Args& a, const EncCtx& c, const SALevel& v, int br) {
+    const int l = v.l;
+    a = {};
+    a.n_prev = v.n_prev;
+    a.m = l < 4 ? kNpoint[l] : 1;
+    a.ns = l < 4 ? kNs[br] : v.n_prev;
     if (l < 4) {
-        b0 = reinterpret_cast<int*>(c.geo + c.L.ball[l][0]);
-        b1 = reinterpret_cast<int*>(c.geo + c.L.ball[l][1]);
-        if (!c.geo_ready) {
-            rc = gp_launch_ball_query2(B, n_prev, kNpoint[l], kRadius[l][0], kRadius[l][1], kNs[0], kNs[1], c.nxyz[l],
-                                       xyz_prev, b0, b1, st);
-            if (rc) return rc;
-        }
+        a.nbr = v.ball[br];
+        a.cent = c.nxyz[l];
+        a.qin = v.qbuf;
+        a.q_stride = proj_stride(l);
+        a.q_off = br == 0 ? 0 : pad16(kWidths[l][0][1]);
     }
-    // layer 0 once per input point for both branches (levels 0-3)
-    float* qbuf = l < 4 ? reinterpret_cast<float*>(c.ws + c.L.proj[l]) : nullptr;
-    if (l < 4) {
-        int q_off = 0;
-        SAArgs pp[2];
-        for (int br = 0; br < 2; ++br) {
-            SAArgs& pa = pp[br];
-            pa = {};
-            pa.n_prev = n_prev;
-            pa.c_prev = c_prev;
-            pa.m = 1;
-            pa.ns = n_prev;
-            pa.cols = n_prev;
-            pa.xyz_prev = xyz_prev;
-            pa.feat_prev = feat_prev;
-            pa.nlayers = 1;
-            const int64_t* o = enc_layer(layer_off, l, br, 0);
-            GP_REQUIRE(o[0] >= 0 && o[1] >= 0, "encoder: missing layer %d/%d/0", l, br);
-            pa.w[0] = wbuf + o[0];
-            pa.bias[0] = wbuf + o[1];
-            pa.kg[0] = (pa.c_prev + 16) / 16;
-            pa.nt[0] = pad16(kWidths[l][br][1]) / 16;
-            pa.proj_out = qbuf;
-            pa.q_stride = proj_stride(l);
-            pa.q_off = q_off;
-            pa.tag = 16 + l * 2 + br;
-            q_off += pad16(kWidths[l][br][1]);
-        }
-        const bool split0 = l >= 1 && enc_layer(layer_off, l, 0, 0)[2] >= 0 && enc_layer(layer_off, l, 1, 0)[2] >= 0;
-        if (l == 0 && c_prev == 0) {   // xyz only: 3 multiply-adds per channel
-            ProjXyzArgs pa = {};
-            pa.xyz = xyz_prev;
-            pa.npts = B * n_prev;
-            for (int br = 0; br < 2; ++br) {
-                pa.w0[br] = pp[br].w[0];
-                pa.b0[br] = pp[br].bias[0];
-                pa.ch[br] = pad16(kWidths[0][br][1]);
-            }
-            GP_REQUIRE(pa.ch[0] + pa.ch[1] == proj_stride(0), "encoder: level-0 projection layout");
-            pa.q = qbuf;
-            pa.q_stride = proj_stride(0);
-            const size_t threads = (size_t)pa.npts * std::max(pa.ch[0], pa.ch[1]) / 4;   // per branch (grid y)
-            hipLaunchKernelGGL(proj_xyz_kernel, dim3((unsigned)((threads + 255) / 256), 2), dim3(256), 0, st, pa);
-            rc = gp_check_launch("proj_xyz_kernel");
-        } else if (l == 0 && !split0 && c_prev % 16 == 0 && pad16(kWidths[0][0][1]) == 16 &&
-                   pad16(kWidths[0][1][1]) == 32) {   // point features at level 0 (DINO-pointwise)
-            ProjFeatArgs pa = {};
-            pa.feat = feat_prev;
-            pa.xyz = xyz_prev;
-            pa.npts = B * n_prev;
-            pa.c_prev = c_prev;
-            for (int br = 0; br < 2; ++br) {
-                pa.w0[br] = pp[br].w[0];
-                pa.b0[br] = pp[br].bias[0];
-            }
-            pa.q = qbuf;
-            pa.q_stride = proj_stride(0);
-            GP_REQUIRE(feat_prev && pa.q_stride == 48, "encoder: level-0 feature projection layout");
-            constexpr int CTW = PROJ_FEAT_CTW;   // points per wave / 16
-            hipLaunchKernelGGL((proj_feat_kernel<1, 2, CTW, PROJ_FEAT_RING>), dim3((pa.npts + 64 * CTW - 1) / (64 * CTW)),
-                               dim3(256), 0, st, pa);
-            rc = gp_check_launch("proj_feat_kernel");
-        } else {
-            rc = split0 ? run_proj_split(c, l, c_prev, feat_prev, xyz_prev, n_prev, qbuf, st)
-                        : launch_pair<4>(pp[0], pp[1], B, st);
-        }
-        if (rc) return rc;
+    a.out = v.out;
+    a.c_out_total = kCout[l];
+    a.out_off = br == 0 ? 0 : kWidths[l][0][l < 4 ? 3 : 2];
+    if constexpr (!std::is_same_v<Args, SAArgs>) {   // layer 0's packed xyz k-group, for the centroid term
+        a.w0 = c.wbuf + enc_layer(c.tab, l, br, 0)[0];
+        a.kg0 = (v.c_prev + 16) / 16;
+        a.gx = v.c_prev / 16;
     }
-    if (l == 4 && enc_layer(layer_off, 4, 0, 0)[2] >= 0 && enc_layer(layer_off, 4, 0, 1)[2] >= 0 &&
-        enc_layer(layer_off, 4, 1, 0)[2] >= 0 && enc_layer(layer_off, 4, 1, 1)[2] >= 0)
-        return run_groupall_split(c, feat_prev, out, st);
-    if (l == 4) {  // group-all pools with atomicMax when a centroid spans workgroups
-        if (hipMemsetAsync(out, 0, sizeof(float) * B * kCout[4], st) != hipSuccess)
-            return gp_check_launch("encoder memset");
+}
+
+static int run_ball_query(const EncCtx& c, const SALevel& v, hipStream_t st) {
+    if (c.geo_ready) return GP_OK;
+    return gp_launch_ball_query2(c.B, v.n_prev, kNpoint[v.l], kRadius[v.l][0], kRadius[v.l][1], kNs[0], kNs[1],
+                                 c.nxyz[v.l], v.xyz_prev, v.ball[0], v.ball[1], st);
+}
+
+struct Layer0 {   // packed fp32 fragments and bias of both branches' layer 0
+    const float* w[2];
+    const float* b[2];
+};
+
+// Level 0 without point features: 3 multiply-adds per channel.
+static int launch_proj_xyz(const EncCtx& c, const SALevel& v, const Layer0& p, hipStream_t st) {
+    ProjXyzArgs pa = {};
+    pa.xyz = v.xyz_prev;
+    pa.npts = c.B * v.n_prev;
+    for (int br = 0; br < 2; ++br) {
+        pa.w0[br] = p.w[br];
+        pa.b0[br] = p.b[br];
+        pa.ch[br] = pad16(kWidths[0][br][1]);
     }
-    if (l <= 1) {   // narrow levels: one launch, wave-independent centroids
-        NarrowArgs na[2];
-        int out_off = 0, q_off = 0;
-        for (int br = 0; br < 2; ++br) {
-            NarrowArgs& n = na[br];
-            n = {};
-            n.qin = qbuf;
-            n.q_stride = proj_stride(l);
-            n.q_off = q_off;
-            q_off += pad16(kWidths[l][br][1]);
-            n.n_prev = n_prev;
-            const int64_t* o0 = enc_layer(layer_off, l, br, 0);
-            const int64_t* o1 = enc_layer(layer_off, l, br, 1);
-            const int64_t* o2 = enc_layer(layer_off, l, br, 2);
-            GP_REQUIRE(o1[0] >= 0 && o2[0] >= 0, "encoder: missing layers of %d/%d", l, br);
-            n.w0 = wbuf + o0[0];
-            n.c_out_total = kCout[l];
-            n.kg0 = (c_prev + 16) / 16;
-            n.gx = c_prev / 16;
-            n.w1 = wbuf + o1[0];
-            n.b1 = wbuf + o1[1];
-            n.w2 = wbuf + o2[0];
-            n.b2 = wbuf + o2[1];
-            n.nbr = br == 0 ? b0 : b1;
-            n.cent = c.nxyz[l];
-            n.m = kNpoint[l];
-            n.ns = kNs[br];
-            n.nobj = B;
-            n.out = out;
-            n.out_off = out_off;
-            out_off += kWidths[l][br][3];
-            n.w1h = o1[2] >= 0 ? wbuf + o1[2] : nullptr;
-            n.w2h = o2[2] >= 0 ? wbuf + o2[2] : nullptr;
-            n.ew1 = (int)o1[3];
-            n.ew2 = (int)o2[3];
-        }
-        FpsSide fs = {};   // nobj = 0: the FPS row of workgroups returns at once
-        if (side) {
-            fs.nlev = l == 0 ? 1 : 2;          // level 0 launch: FPS level 1; level 1 launch: FPS levels 2, 3
-            fs.in = c.nxyz[l];
-            fs.nobj = B;
-            for (int k = 0; k < fs.nlev; ++k) {
-                const int lv = l == 0 ? 1 : 2 + k;
-                fs.n[k] = c.nin[lv];
-                fs.m[k] = c.mout[lv];
-                const FpsGeom g = fps_geom(c.nin[lv]);
-                fs.nb[k] = g.nb;
-                fs.jbits[k] = g.jbits;
-                fs.idx[k] = c.fidx[lv];
-                fs.nxyz[k] = c.nxyz[lv];
-            }
-        }
-        const dim3 grid(std::max(512, B), 3);
-        if (l == 0 && na[1].w1h && na[1].w2h) {
-            const size_t lds = std::max({narrow_lds(1, 1, 2), narrow_split_lds(1, 2, 4), fps_side_lds(fs)});
-#ifdef GP_NARROW_SEQ   // diagnostic builds only: the two branches as two launches (no co-resident mix)
-            NarrowArgs n0 = na[0], n1 = na[1];
-            n0.nobj = 0;
-            n1.nobj = 0;
-            hipLaunchKernelGGL((sa_narrow_mixed_kernel<1, 1, 2, 1, 1, 2, 4, 2>), grid, dim3(SA_THREADS), lds, st,
-                               na[0], n1, fs);
-            hipLaunchKernelGGL((sa_narrow_mixed_kernel<1, 1, 2, 1, 1, 2, 4, 2>), grid, dim3(SA_THREADS), lds, st,
-                               n0, na[1], FpsSide{});
-#else
-            hipLaunchKernelGGL((sa_narrow_mixed_kernel<1, 1, 2, 1, 1, 2, 4, 2>), grid, dim3(SA_THREADS), lds, st,
-                               na[0], na[1], fs);
-#endif
-        } else if (l == 0) {
-            const size_t lds = std::max({narrow_lds(1, 1, 2), narrow_lds(2, 2, 4), fps_side_lds(fs)});
-            hipLaunchKernelGGL((sa_narrow_kernel<1, 1, 2, 1, 2, 2, 4, 2>), grid, dim3(SA_THREADS), lds, st, na[0],
-                               na[1], fs);
-        } else if (na[0].w1h && na[0].w2h && na[1].w1h && na[1].w2h) {
-            const size_t lds = std::max({narrow_split_lds(2, 4, 8), narrow_split_lds(2, 6, 8), fps_side_lds(fs)});
-            hipLaunchKernelGGL((sa_narrow_split_kernel<2, 4, 8, 1, 2, 6, 8, 2>), grid, dim3(SA_THREADS), lds, st,
-                               na[0], na[1], fs);
-        } else {
-            const size_t lds = std::max({narrow_lds(4, 4, 8), narrow_lds(4, 6, 8), fps_side_lds(fs)});
-            hipLaunchKernelGGL((sa_narrow_kernel<4, 4, 8, 1, 4, 6, 8, 2>), grid, dim3(SA_THREADS), lds, st, na[0],
-                               na[1], fs);
-        }
-        return gp_check_launch("sa_narrow_kernel");
+    GP_REQUIRE(pa.ch[0] + pa.ch[1] == proj_stride(0), "encoder: level-0 projection layout");
+    pa.q = v.qbuf;
+    pa.q_stride = proj_stride(0);
+    const size_t threads = (size_t)pa.npts * std::max(pa.ch[0], pa.ch[1]) / 4;   // per branch (grid y)
+    hipLaunchKernelGGL(proj_xyz_kernel, dim3((unsigned)((threads + 255) / 256), 2), dim3(256), 0, st, pa);
+    return gp_check_launch("proj_xyz_kernel");
+}
+
+// Level 0 with point features (DINO-pointwise).
+static int launch_proj_feat(const EncCtx& c, const SALevel& v, const Layer0& p, hipStream_t st) {
+    ProjFeatArgs pa = {};
+    pa.feat = v.feat_prev;
+    pa.xyz = v.xyz_prev;
+    pa.npts = c.B * v.n_prev;
+    pa.c_prev = v.c_prev;
+    for (int br = 0; br < 2; ++br) {
+        pa.w0[br] = p.w[br];
+        pa.b0[br] = p.b[br];
     }
-    // levels 2-3: split-f16 kernel when the table carries the planes (pack.pack_encoder)
-    if ((l == 2 || l == 3) && enc_layer(layer_off, l, 0, 1)[2] >= 0 && enc_layer(layer_off, l, 0, 2)[2] >= 0 &&
-        enc_layer(layer_off, l, 1, 1)[2] >= 0 && enc_layer(layer_off, l, 1, 2)[2] >= 0) {
-        const int CT = l == 2 ? SPLIT_CT2 : SPLIT_CT3;
-        SplitArgs sp[2];
-        int off_out = 0;
-        for (int br = 0; br < 2; ++br) {
-            SplitArgs& a = sp[br];
-            a = {};
-            a.n_prev = n_prev;
-            a.m = kNpoint[l];
-            a.ns = kNs[br];
-            a.cols = a.m * a.ns;
-            a.qin = qbuf;
-            a.q_stride = proj_stride(l);
-            a.q_off = br == 0 ? 0 : pad16(kWidths[l][0][1]);
-            const int64_t* o0 = enc_layer(layer_off, l, br, 0);
-            a.w0 = wbuf + o0[0];
-            a.kg0 = (c_prev + 16) / 16;
-            a.gx = c_prev / 16;
-            a.nbr = br == 0 ? b0 : b1;
-            a.cent = c.nxyz[l];
-            for (int i = 0; i < 2; ++i) {
-                const int64_t* o = enc_layer(layer_off, l, br, i + 1);
-                a.w[i] = wbuf + o[2];
-                a.bias[i] = wbuf + o[1];
-                a.ew[i] = (int)o[3];
-            }
-            a.out = out;
-            a.c_out_total = kCout[l];
-            a.out_off = off_out;
-            a.tag = l * 2 + br;
-            off_out += kWidths[l][br][3];
-            GP_REQUIRE((16 * CT) % a.ns == 0, "encoder: level %d centroids of %d columns straddle %d-column tiles",
-                       l, a.ns, 16 * CT);
-        }
-        const int cmax = std::max(sp[0].cols, sp[1].cols);
-        const dim3 grid((cmax + 16 * CT - 1) / (16 * CT), B, 2), blk(SPLIT_WV * 64);
-        if (l == 2) {
-            const size_t lds = sa_split_lds<SPLIT_CT2, 4, 7>();
-            hipLaunchKernelGGL((sa_split_kernel<SPLIT_CT2, SPLIT_D2, 4, 7, 8, 7, 8, 2>), grid, blk, lds, st, sp[0], sp[1]);
-        } else {
-            const size_t lds = std::max(sa_split_lds<SPLIT_CT3, 8, 8>(), sa_split_lds<SPLIT_CT3, 8, 12>());
-            hipLaunchKernelGGL((sa_split_kernel<SPLIT_CT3, SPLIT_D3, 8, 8, 16, 12, 16>), grid, blk, lds, st, sp[0],
-                               sp[1]);
-        }
-        return gp_check_launch("sa_split_kernel");
+    pa.q = v.qbuf;
+    pa.q_stride = proj_stride(0);
+    GP_REQUIRE(v.feat_prev && pa.q_stride == 48, "encoder: level-0 feature projection layout");
+    constexpr int CTW = PROJ_FEAT_CTW;   // points per wave / 16
+    hipLaunchKernelGGL((proj_feat_kernel<1, 2, CTW, PROJ_FEAT_RING>), dim3((pa.npts + 64 * CTW - 1) / (64 * CTW)),
+                       dim3(256), 0, st, pa);
+    return gp_check_launch("proj_feat_kernel");
+}
+
+// Exact fp32 MFMA: the points as one-layer, unpooled columns of sa_pair_kernel.
+static int launch_proj_pair(const EncCtx& c, const SALevel& v, const Layer0& p, hipStream_t st) {
+    SAArgs pp[2];
+    for (int br = 0; br < 2; ++br) {
+        SAArgs& pa = pp[br];
+        pa = {};
+        pa.n_prev = v.n_prev;
+        pa.c_prev = v.c_prev;
+        pa.m = 1;
+        pa.ns = v.n_prev;
+        pa.cols = v.n_prev;
+        pa.xyz_prev = v.xyz_prev;
+        pa.feat_prev = v.feat_prev;
+        pa.nlayers = 1;
+        pa.w[0] = p.w[br];
+        pa.bias[0] = p.b[br];
+        pa.kg[0] = (v.c_prev + 16) / 16;
+        pa.nt[0] = pad16(kWidths[v.l][br][1]) / 16;
+        pa.proj_out = v.qbuf;
+        pa.q_stride = proj_stride(v.l);
+        pa.q_off = br == 0 ? 0 : pad16(kWidths[v.l][0][1]);
+        pa.tag = 16 + v.l * 2 + br;
     }
-    int out_off = 0;
+    return launch_pair<4>(pp[0], pp[1], c.B, st);
+}
+
+// Layer 0 once per input point for both branches (levels 0-3).
+static int run_projection(const EncCtx& c, const SALevel& v, hipStream_t st) {
+    const int l = v.l;
+    Layer0 p;
+    for (int br = 0; br < 2; ++br) {
+        const int64_t* o = enc_layer(c.tab, l, br, 0);
+        GP_REQUIRE(o[0] >= 0 && o[1] >= 0, "encoder: missing layer %d/%d/0", l, br);
+        p.w[br] = c.wbuf + o[0];
+        p.b[br] = c.wbuf + o[1];
+    }
+    const bool split0 = l >= 1 && has_split(c.tab, l, 0, 0) && has_split(c.tab, l, 1, 0);
+    if (l == 0 && v.c_prev == 0) return launch_proj_xyz(c, v, p, st);
+    if (l == 0 && !split0 && v.c_prev % 16 == 0 && pad16(kWidths[0][0][1]) == 16 && pad16(kWidths[0][1][1]) == 32)
+        return launch_proj_feat(c, v, p, st);
+    return split0 ? run_proj_split(c, l, v.c_prev, v.feat_prev, v.xyz_prev, v.n_prev, v.qbuf, st)
+                  : launch_proj_pair(c, v, p, st);
+}
+
+// FPS levels that ride along a narrow level's launch: level 1 beside level 0, levels 2 and 3 beside level 1.
+static FpsSide fps_side_work(const EncCtx& c, int l, bool side) {
+    FpsSide fs = {};   // nobj = 0: the FPS row of workgroups returns at once
+    if (!side) return fs;
+    fs.nlev = l == 0 ? 1 : 2;
+    fs.in = c.nxyz[l];
+    fs.nobj = c.B;
+    for (int k = 0; k < fs.nlev; ++k) {
+        const int lv = l == 0 ? 1 : 2 + k;
+        fs.n[k] = c.nin[lv];
+        fs.m[k] = c.mout[lv];
+        const FpsGeom g = fps_geom(c.nin[lv]);
+        fs.nb[k] = g.nb;
+        fs.jbits[k] = g.jbits;
+        fs.idx[k] = c.fidx[lv];
+        fs.nxyz[k] = c.nxyz[lv];
+    }
+    return fs;
+}
+
+// Narrow levels 0-1: one launch, wave-independent centroids; a branch runs split-f16 when the table carries
+// its planes (level 0: the 32-wide branch only).
+static int run_narrow_level(const EncCtx& c, const SALevel& v, bool side, hipStream_t st) {
+    const int l = v.l;
+    NarrowArgs na[2];
+    for (int br = 0; br < 2; ++br) {
+        NarrowArgs& n = na[br];
+        fill_branch(n, c, v, br);
+        const int64_t* o1 = enc_layer(c.tab, l, br, 1);
+        const int64_t* o2 = enc_layer(c.tab, l, br, 2);
+        GP_REQUIRE(o1[0] >= 0 && o2[0] >= 0, "encoder: missing layers of %d/%d", l, br);
+        n.w1 = c.wbuf + o1[0];
+        n.b1 = c.wbuf + o1[1];
+        n.w2 = c.wbuf + o2[0];
+        n.b2 = c.wbuf + o2[1];
+        n.nobj = c.B;
+        n.w1h = o1[2] >= 0 ? c.wbuf + o1[2] : nullptr;
+        n.w2h = o2[2] >= 0 ? c.wbuf + o2[2] : nullptr;
+        n.ew1 = (int)o1[3];
+        n.ew2 = (int)o2[3];
+    }
+    const FpsSide fs = fps_side_work(c, l, side);
+    const bool h0 = na[0].w1h && na[0].w2h, h1 = na[1].w1h && na[1].w2h;
+    if (l == 0 && h1) return launch_narrow<NarrowF32<1, 1, 2, 1>, NarrowSplit<1, 2, 4, 2>>(na[0], na[1], fs, st);
+    if (l == 0) return launch_narrow<NarrowF32<1, 1, 2, 1>, NarrowF32<2, 2, 4, 2>>(na[0], na[1], fs, st);
+    if (h0 && h1) return launch_narrow<NarrowSplit<2, 4, 8, 1>, NarrowSplit<2, 6, 8, 2>>(na[0], na[1], fs, st);
+    return launch_narrow<NarrowF32<4, 4, 8, 1>, NarrowF32<4, 6, 8, 2>>(na[0], na[1], fs, st);
+}
+
+// Levels 2-3 in split-f16, when the table carries the planes of layers 1-2 (pack.pack_encoder).
+static int run_split_level(const EncCtx& c, const SALevel& v, hipStream_t st) {
+    const int l = v.l, CT = l == 2 ? SPLIT_CT2 : SPLIT_CT3;
+    SplitArgs sp[2];
+    for (int br = 0; br < 2; ++br) {
+        SplitArgs& a = sp[br];
+        fill_branch(a, c, v, br);
+        a.cols = a.m * a.ns;
+        for (int i = 0; i < 2; ++i) {
+            const int64_t* o = enc_layer(c.tab, l, br, i + 1);
+            a.w[i] = c.wbuf + o[2];
+            a.bias[i] = c.wbuf + o[1];
+            a.ew[i] = (int)o[3];
+        }
+        a.tag = l * 2 + br;
+        GP_REQUIRE((16 * CT) % a.ns == 0, "encoder: level %d centroids of %d columns straddle %d-column tiles", l,
+                   a.ns, 16 * CT);
+    }
+    const int cmax = std::max(sp[0].cols, sp[1].cols);
+    const dim3 grid((cmax + 16 * CT - 1) / (16 * CT), c.B, 2), blk(SPLIT_WV * 64);
+    if (l == 2) {
+        const size_t lds = sa_split_lds<SPLIT_CT2, 4, 7>();
+        hipLaunchKernelGGL((sa_split_kernel<SPLIT_CT2, SPLIT_D2, 4, 7, 8, 7, 8, 2>), grid, blk, lds, st, sp[0], sp[1]);
+    } else {
+        const size_t lds = std::max(sa_split_lds<SPLIT_CT3, 8, 8>(), sa_split_lds<SPLIT_CT3, 8, 12>());
+        hipLaunchKernelGGL((sa_split_kernel<SPLIT_CT3, SPLIT_D3, 8, 8, 16, 12, 16>), grid, blk, lds, st, sp[0], sp[1]);
+    }
+    return gp_check_launch("sa_split_kernel");
+}
+
+// Levels 2-3 and GroupAll in exact fp32 MFMA, both branches per launch, 32 columns per workgroup (LDS
+// ping-pong <= 80 KiB: 2-3 workgroups per CU); GroupAll is split over 2 workgroups per (object, branch)
+// with atomicMax pooling.
+// Levels 3-4: one pass of up to 8 tiles per wave per layer (2 workgroups per CU either way); level 2
+// keeps 4-tile passes: its 131 VGPRs fit 3 workgroups per CU, a 7-tile pass's 191 only 2 (measured 725
+// vs 764 us).
+static int run_pair_level(const EncCtx& c, const SALevel& v, hipStream_t st) {
+    const int l = v.l;
     SAArgs sa[2];
     for (int br = 0; br < 2; ++br) {
         SAArgs& a = sa[br];
-        a = {};
-        a.n_prev = n_prev;
-        a.c_prev = c_prev;
-        a.m = l < 4 ? kNpoint[l] : 1;
-        a.ns = l < 4 ? kNs[br] : n_prev;
+        fill_branch(a, c, v, br);
+        a.c_prev = v.c_prev;
         a.cols = a.m * a.ns;
-        a.xyz_prev = xyz_prev;
-        a.feat_prev = feat_prev;
-        a.cent = l < 4 ? c.nxyz[l] : nullptr;
-        a.nbr = l < 4 ? (br == 0 ? b0 : b1) : nullptr;
+        a.xyz_prev = v.xyz_prev;
+        a.feat_prev = v.feat_prev;
         a.nlayers = l < 4 ? 3 : 2;
         for (int i = 0; i < a.nlayers; ++i) {
-            const int64_t* o = enc_layer(layer_off, l, br, i);
+            const int64_t* o = enc_layer(c.tab, l, br, i);
             GP_REQUIRE(o[0] >= 0 && o[1] >= 0, "encoder: missing layer %d/%d/%d", l, br, i);
-            a.w[i] = wbuf + o[0];
-            a.bias[i] = wbuf + o[1];
+            a.w[i] = c.wbuf + o[0];
+            a.bias[i] = c.wbuf + o[1];
             const int kin = i == 0 ? a.c_prev + 16 : pad16(kWidths[l][br][i]);
             a.kg[i] = kin / 16;
             a.nt[i] = pad16(kWidths[l][br][i + 1]) / 16;
         }
-        a.out = out;
         a.tag = l * 2 + br;
-        if (l < 4) {
-            a.qin = qbuf;
-            a.q_stride = proj_stride(l);
-            a.q_off = br == 0 ? 0 : pad16(kWidths[l][0][1]);
-        }
-        a.c_out_total = kCout[l];
-        a.out_off = out_off;
-        out_off += kWidths[l][br][a.nlayers];
         if (a.ns % 16 != 0) {
             gp_set_error("encoder: nsample %d not a multiple of 16", a.ns);
             return GP_ERR_UNSUPPORTED;
         }
     }
-    // levels 2-3 at 32 columns (LDS ping-pong <= 80 KiB: 2-3 workgroups per CU), GroupAll split
-    // over 2 workgroups per (object, branch) with atomicMax pooling; both branches per launch
-    // levels 3-4: one pass of up to 8 tiles per wave per layer (2 workgroups per CU either way);
-    // level 2 keeps 4-tile passes: its 131 VGPRs fit 3 workgroups per CU, a 7-tile pass's 191 only
-    // 2 (measured 725 vs 764 us)
-    return l == 2 ? launch_pair<2, 4>(sa[0], sa[1], B, st) : launch_pair<2, 8>(sa[0], sa[1], B, st);
+    return l == 2 ? launch_pair<2, 4>(sa[0], sa[1], c.B, st) : launch_pair<2, 8>(sa[0], sa[1], c.B, st);
+}
+
+// GroupAll: two split-f16 token GEMMs when the table carries both layers' planes, else the fp32 pair form,
+// which pools with atomicMax (a centroid spans workgroups) into a zeroed output.
+static int run_groupall(const EncCtx& c, const SALevel& v, hipStream_t st) {
+    if (level_split(c.tab, 4, 0, 1)) return run_groupall_split(c, v.feat_prev, v.out, st);
+    if (hipMemsetAsync(v.out, 0, sizeof(float) * c.B * kCout[4], st) != hipSuccess)
+        return gp_check_launch("encoder memset");
+    return run_pair_level(c, v, st);
+}
+
+// One SA level l (ball query, per-point layer 0, layers 1-2 + max-pool) over the FPS results already
+// in the workspace. feat_prev (B, n_prev, c_prev) point-major or null (c_prev = 0); out (B, M_l, C_l).
+// side: FPS levels that ride along as extra workgroups of the narrow launches (gp_encoder_forward),
+// or false when the FPS chain ran whole beforehand (gp_encoder_fps).
+static int run_sa_level(const EncCtx& c, int l, int c_prev, const float* feat_prev, float* out, bool side,
+                        hipStream_t st) {
+    SALevel v = {};
+    v.l = l;
+    v.c_prev = c_prev;
+    v.n_prev = l == 0 ? c.N : kNpoint[l - 1];
+    v.xyz_prev = l == 0 ? c.pts : c.nxyz[l - 1];
+    v.feat_prev = feat_prev;
+    v.out = out;
+    if (l == 4) return run_groupall(c, v, st);
+    v.ball[0] = reinterpret_cast<int*>(c.geo + c.L.ball[l][0]);
+    v.ball[1] = reinterpret_cast<int*>(c.geo + c.L.ball[l][1]);
+    v.qbuf = reinterpret_cast<float*>(c.ws + c.L.proj[l]);
+    int rc = run_ball_query(c, v, st);
+    if (rc) return rc;
+    rc = run_projection(c, v, st);
+    if (rc) return rc;
+    if (l <= 1) return run_narrow_level(c, v, side, st);
+    if (level_split(c.tab, l, 1, 2)) return run_split_level(c, v, st);
+    return run_pair_level(c, v, st);
 }
 
 static int enc_check(const float* wbuf, const int64_t* layer_off, const float* pts, int B, int N, void* workspace,
@@ -1996,18 +1937,12 @@ extern "C" int gp_encoder_forward(const float* wbuf, const int64_t* layer_off, c
     GP_REQUIRE(feat, "encoder_forward: null feat");
     const EncCtx c = enc_ctx(wbuf, layer_off, pts, B, N, workspace);
     // FPS level 0 here; levels 1-3 run beside the level-0 / level-1 MLP launches (FpsSide)
-#ifdef GP_NO_FPS_SIDE   // diagnostic builds only: the whole FPS chain up front, no FPS workgroups beside the MLPs
-    rc = gp_launch_fps_chain(pts, B, 4, c.nin, c.mout, (int* const*)c.fidx, (float* const*)c.nxyz, st);
-    constexpr bool side = false;
-#else
     rc = gp_launch_fps_chain(pts, B, 1, c.nin, c.mout, (int* const*)c.fidx, (float* const*)c.nxyz, st);
-    constexpr bool side = true;
-#endif
     if (rc) return rc;
     for (int l = 0; l < 5; ++l) {
         const float* fprev = l == 0 ? nullptr : reinterpret_cast<const float*>(c.ws + c.L.feat[l - 1]);
         float* out = l < 4 ? reinterpret_cast<float*>(c.ws + c.L.feat[l]) : feat;
-        rc = run_sa_level(c, l, l == 0 ? 0 : kCout[l - 1], fprev, out, side, st);
+        rc = run_sa_level(c, l, l == 0 ? 0 : kCout[l - 1], fprev, out, true, st);
         if (rc) return rc;
     }
     return GP_OK;

@@ -86,7 +86,7 @@ class EncoderModel:
 
     def set_arith(self, arith: str) -> None:
         """GEMM arithmetic of SA levels 1-3 and GroupAll: "split_f16" (f16 hi/lo MFMA products with
-        per-column activation scaling: sa_narrow_split_kernel, sa_split_kernel, tok_split_gemm_kernel)
+        per-column activation scaling: sa_narrow_kernel, sa_split_kernel, tok_split_gemm_kernel)
         or "f32" (exact fp32 MFMA)."""
         if arith not in ("split_f16", "f32"):
             raise ValueError(f"unknown encoder arithmetic {arith!r} (split_f16 | f32)")

@@ -48,8 +48,8 @@ def pad_vec(b: np.ndarray, n: int) -> np.ndarray:
 # ---------------------------------------------------------------- encoder
 ENC_SPLIT_LEVELS = (1, 2, 3, 4)   # levels whose every layer also gets split-f16 planes: layer 0 of levels 1-3 and
                                   # both GroupAll layers run as token GEMMs (tok_split_gemm_kernel), layers 1-2 of
-                                  # level 1 in sa_narrow_split_kernel, of levels 2-3 in sa_split_kernel; level 0
-                                  # has planes for layers 1-2 (its 32-wide branch in sa_narrow_mixed_kernel)
+                                  # level 1 in sa_narrow_kernel (NarrowSplit), of levels 2-3 in sa_split_kernel; level 0
+                                  # has planes for layers 1-2 (its 32-wide branch, NarrowSplit in sa_narrow_kernel)
 
 
 def enc_split_layer(lv: int, i: int) -> bool:

@@ -1,9 +1,10 @@
 """Compare the gfx950 ISA of kernels between two builds of libgenpose_hip.so (tuning aid, not a test).
 
-    python scripts/isa_diff.py OLD.so NEW.so [regex]     # default regex: every kernel
+    python scripts/isa_diff.py OLD.so NEW.so [regex] [OLD_REGEX=NEW_TEXT ...]   # default regex: every kernel
 
 Prints, per kernel matching the regex, whether the instruction streams (addresses and branch offsets
-stripped) are identical, else the instruction counts and the first differing lines.
+stripped) are identical, else the instruction counts and the first differing lines. Each OLD_REGEX=NEW_TEXT
+renames the old library's kernels (re.sub on the mangled name) before they are paired with the new one's.
 """
 import os
 import re
@@ -37,7 +38,11 @@ def kernels(so):
 
 def main():
     a, b = kernels(sys.argv[1]), kernels(sys.argv[2])
-    pat = re.compile(sys.argv[3] if len(sys.argv) > 3 else ".")
+    renames = [x.split("=", 1) for x in sys.argv[3:] if "=" in x]
+    regex = [x for x in sys.argv[3:] if "=" not in x]
+    for old, new in renames:
+        a = {re.sub(old, new, fn): ins for fn, ins in a.items()}
+    pat = re.compile(regex[0] if regex else ".")
     for fn in sorted(set(a) | set(b)):
         if not pat.search(fn):
             continue
