@@ -274,6 +274,11 @@ def check(rc: int, what: str = "") -> None:
         raise GenPoseHipError(f"{what or 'genpose_hip'} failed ({rc}): {msg}")
 
 
+def vp(t) -> ctypes.c_void_p:
+    """A device tensor's address as a C pointer argument (None: a null pointer)."""
+    return c_void_p(None if t is None else t.data_ptr())
+
+
 def exported_symbols(path: str = LIB_PATH) -> Iterable[str]:
     lib = ctypes.CDLL(path)
     return [n for n in _SIGS if hasattr(lib, n)]

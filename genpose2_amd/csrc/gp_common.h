@@ -15,6 +15,9 @@ int gp_check_launch(const char* what);
 // the split linear with implicit im2col of a 3x3 conv (gp_fusion.hip; used by the image encoder, not part of the ABI)
 int gp_linear_split_conv3x3(const float* f, int b, int g, int d, const int32_t* wpk, const float* bias, int n,
                             float* y, const float* rmax, hipStream_t st);
+// rmax[r] = max |x[r][0 .. k)| for m rows of stride ldx (k % 4 == 0, 16-byte aligned rows; gp_fusion.hip, not part
+// of the ABI): the row maxima the split linears scale their tokens by
+int gp_rowmax_abs(const float* x, int ldx, int m, int k, float* rmax, hipStream_t st);
 
 #define GP_REQUIRE(cond, ...)                   \
     do {                                        \
@@ -22,6 +25,12 @@ int gp_linear_split_conv3x3(const float* f, int b, int g, int d, const int32_t* 
             gp_set_error(__VA_ARGS__);          \
             return GP_ERR_INVALID;              \
         }                                       \
+    } while (0)
+// return a callee's status unless it is GP_OK
+#define GP_TRY(expr)                      \
+    do {                                  \
+        const int rc_ = (expr);           \
+        if (rc_ != GP_OK) return rc_;     \
     } while (0)
 
 // --------------------------------------------------------------- MFMA (exact f32)

@@ -30,12 +30,6 @@ constexpr int DN_MAX_PATCHES = 1024;
 constexpr int DN_CHUNK_ROWS = 85 * 256;
 constexpr float DN_EPS = 1e-5f;
 
-#define DN_TRY(x)                         \
-    do {                                  \
-        const int rc_ = (x);              \
-        if (rc_ != GP_OK) return rc_;     \
-    } while (0)
-
 // ============================================================================ prefix tokens
 // h[img, t, :] = cls (t = 0) or storage_tokens[t - 1] (t = 1..4); one float4 per thread
 __global__ __launch_bounds__(DN_THREADS) void dino_prefix_kernel(const float* __restrict__ cls,
@@ -50,7 +44,7 @@ __global__ __launch_bounds__(DN_THREADS) void dino_prefix_kernel(const float* __
 }
 
 // ============================================================================ patch embedding
-// h[img, 5 + p, o] = sum_k patch(img, p)[k] w[o, k] + bias[o], k = c * 256 + ky * 16 + kx. linear_kernel's wave
+// h[img, 5 + p, o] = sum_k patch(img, p)[k] w[o, k] + bias[o], k = c * 256 + ky * 16 + kx. gemm_nt_body's wave
 // layout (4 waves as 2 patch tiles x 2 output groups, a wave owns 2 patch tiles x 4 output tiles of 16): the
 // 16-deep k-group g is image row ky = g % 16 of channel g / 16, and lane (q, r) reads its pixels 4q .. 4q + 3.
 __global__ __launch_bounds__(DN_THREADS) void dino_patch_embed_kernel(const float* __restrict__ rgb, int imgs, int H,
@@ -409,10 +403,10 @@ extern "C" int gp_dino_forward(const gp_dino_weights* wt, const float* rgb, int 
         const float* x = rgb + (size_t)b0 * 3 * h * w;
         hipLaunchKernelGGL(dino_prefix_kernel, dim3((cb * DN_PREFIX * DN_D / 4 + DN_THREADS - 1) / DN_THREADS),
                            dim3(DN_THREADS), 0, st, wt->cls_token, wt->storage_tokens, cb, n, hbuf);
-        DN_TRY(gp_check_launch("dino_prefix_kernel"));
+        GP_TRY(gp_check_launch("dino_prefix_kernel"));
         hipLaunchKernelGGL(dino_patch_embed_kernel, dim3((cb * np + 63) / 64, DN_D / 128), dim3(DN_THREADS), 0, st, x, cb,
                            h, w, wt->patch_w, wt->patch_b, hbuf);
-        DN_TRY(gp_check_launch("dino_patch_embed_kernel"));
+        GP_TRY(gp_check_launch("dino_patch_embed_kernel"));
         const float* pending = nullptr;   // fp32 path: a linear's output not yet added to h
         auto add_ln = [&](const float* gamma, const float* beta, float* dst, float* dmax, int drop) {
             hipLaunchKernelGGL(dino_add_ln_kernel, dim3((m + 3) / 4), dim3(DN_THREADS), 0, st, hbuf, pending, m, gamma,
@@ -422,42 +416,42 @@ extern "C" int gp_dino_forward(const gp_dino_weights* wt, const float* rgb, int 
         };
         for (int l = 0; l < nblk; ++l) {
             const gp_dino_block& k = wt->blocks[l];
-            DN_TRY(add_ln(k.ln1_w, k.ln1_b, y, split ? ymx : nullptr, 0));
+            GP_TRY(add_ln(k.ln1_w, k.ln1_b, y, split ? ymx : nullptr, 0));
             if (split)
-                DN_TRY(gp_linear_split(y, DN_D, m, DN_D, k.qkv_h, k.qkv_b, 3 * DN_D, 0, qkv, 3 * DN_D, ymx,
+                GP_TRY(gp_linear_split(y, DN_D, m, DN_D, k.qkv_h, k.qkv_b, 3 * DN_D, 0, qkv, 3 * DN_D, ymx,
                                        GP_LINEAR_RMAX_GIVEN, nullptr, st));
             else
-                DN_TRY(gp_linear(y, DN_D, m, DN_D, k.qkv_w, k.qkv_b, 3 * DN_D, 0, qkv, 3 * DN_D, st));
+                GP_TRY(gp_linear(y, DN_D, m, DN_D, k.qkv_w, k.qkv_b, 3 * DN_D, 0, qkv, 3 * DN_D, st));
             if (split && hipMemsetAsync(amx, 0, sizeof(float) * (size_t)m, st) != hipSuccess)
                 return gp_check_launch("dino attention ymax memset");
             hipLaunchKernelGGL(dino_attention_kernel, dim3((unsigned)(nqb * DN_HEADS * cb)), dim3(DN_THREADS), 0, st, qkv,
                                wt->rope, n, nqb, att, split ? reinterpret_cast<unsigned*>(amx) : nullptr);
-            DN_TRY(gp_check_launch("dino_attention_kernel"));
+            GP_TRY(gp_check_launch("dino_attention_kernel"));
             if (split) {
-                DN_TRY(gp_linear_split(att, DN_D, m, DN_D, k.proj_h, k.proj_b, DN_D, 4, hbuf, DN_D, amx,
+                GP_TRY(gp_linear_split(att, DN_D, m, DN_D, k.proj_h, k.proj_b, DN_D, 4, hbuf, DN_D, amx,
                                        GP_LINEAR_RMAX_GIVEN, nullptr, st));
             } else {
-                DN_TRY(gp_linear(att, DN_D, m, DN_D, k.proj_w, k.proj_b, DN_D, 0, rbuf, DN_D, st));
+                GP_TRY(gp_linear(att, DN_D, m, DN_D, k.proj_w, k.proj_b, DN_D, 0, rbuf, DN_D, st));
                 pending = rbuf;
             }
-            DN_TRY(add_ln(k.ln2_w, k.ln2_b, y, split ? ymx : nullptr, 0));
+            GP_TRY(add_ln(k.ln2_w, k.ln2_b, y, split ? ymx : nullptr, 0));
             if (split) {
-                DN_TRY(gp_linear_split(y, DN_D, m, DN_D, k.w12_h, k.w12_b, 2 * DN_HID, 5, g, DN_HID, ymx,
+                GP_TRY(gp_linear_split(y, DN_D, m, DN_D, k.w12_h, k.w12_b, 2 * DN_HID, 5, g, DN_HID, ymx,
                                        GP_LINEAR_RMAX_GIVEN, gmx, st));
-                DN_TRY(gp_linear_split(g, DN_HID, m, DN_HID, k.w3_h, k.w3_b, DN_D, 4, hbuf, DN_D, gmx,
+                GP_TRY(gp_linear_split(g, DN_HID, m, DN_HID, k.w3_h, k.w3_b, DN_D, 4, hbuf, DN_D, gmx,
                                        GP_LINEAR_RMAX_GIVEN, nullptr, st));
             } else {
-                DN_TRY(gp_linear(y, DN_D, m, DN_D, k.w12_w, k.w12_b, 2 * DN_HID, 0, u, 2 * DN_HID, st));
+                GP_TRY(gp_linear(y, DN_D, m, DN_D, k.w12_w, k.w12_b, 2 * DN_HID, 0, u, 2 * DN_HID, st));
                 const size_t total4 = (size_t)m * (DN_HID / 4);
                 hipLaunchKernelGGL(dino_swiglu_kernel, dim3((unsigned)((total4 + DN_THREADS - 1) / DN_THREADS)),
                                    dim3(DN_THREADS), 0, st, u, total4, g);
-                DN_TRY(gp_check_launch("dino_swiglu_kernel"));
-                DN_TRY(gp_linear(g, DN_HID, m, DN_HID, k.w3_w, k.w3_b, DN_D, 0, rbuf, DN_D, st));
+                GP_TRY(gp_check_launch("dino_swiglu_kernel"));
+                GP_TRY(gp_linear(g, DN_HID, m, DN_HID, k.w3_w, k.w3_b, DN_D, 0, rbuf, DN_D, st));
                 pending = rbuf;
             }
             for (int i = 0; i < n_out; ++i)
                 if (out_layers[i] == l)
-                    DN_TRY(add_ln(wt->norm_w, wt->norm_b, outs[i] + (size_t)b0 * np * DN_D, nullptr, DN_PREFIX));
+                    GP_TRY(add_ln(wt->norm_w, wt->norm_b, outs[i] + (size_t)b0 * np * DN_D, nullptr, DN_PREFIX));
         }
     }
     return GP_OK;

@@ -9,84 +9,44 @@
 //   * GatedAttentionFusion's channel / spatial attention and gating (attention.py:284-325).
 // Token tensors are point-major (b, n, C): the reference's (b, C, n) transposed, so one token's channels
 // are contiguous and every linear is a row-major GEMM over b*n rows.
+#include <type_traits>
+
 #include "gp_common.h"
-#include "gp_head.h"   // split-f16 helpers: f16x8, mfma_h, exp2i, ilog2f, rows_max
+#include "gp_gemm_nt.h"   // gemm_nt_body
+#include "gp_head.h"      // split-f16 helpers: f16x8, mfma_h, exp2i, ilog2f, rows_max
 
 constexpr int FUS_THREADS = 256;
-#define FUS_TRY(x)                        \
-    do {                                  \
-        const int rc_ = (x);              \
-        if (rc_ != GP_OK) return rc_;     \
-    } while (0)
 constexpr int FUS_HEADS = 8;
 
 __device__ __forceinline__ float sigmoidf(float v) { return 1.0f / (1.0f + expf(-v)); }
 
+// f(std::integral_constant<int, act>) for the runtime act in 0 .. N - 1 (the callers have checked the range): the
+// kernels take their activation as a template argument
+template <int N, class F>
+static void with_act(int act, F f) {
+    if constexpr (N > 1) {
+        if (act < N - 1) return with_act<N - 1>(act, f);
+    }
+    f(std::integral_constant<int, N - 1>{});
+}
+
 // ============================================================================ token linear (MFMA)
-// y[r, o] = act(sum_k x[r, k] w[o, k] + bias[o]). 4 waves as 2 (tokens) x 2 (outputs); a wave owns TM
-// token tiles x TN output tiles of 16. MFMA A = w rows (output channels), B = x rows (tokens): lane
-// (q, r) feeds float4 k-slices 16g + 4q .. +3 of row r of both, so one 16-deep k-group is 4 MFMAs per
-// tile pair and the accumulator holds 4 consecutive output channels of one token (a float4 store).
+// y[r, o] = act(sum_k x[r, k] w[o, k] + bias[o]): gemm_nt_body over the token rows of x and the output rows of w,
+// a wave owning TM token tiles x TN output tiles of 16; the bias (or zero) and the activation are its epilogue.
 template <int TM, int TN, int ACT>
 __global__ __launch_bounds__(FUS_THREADS) void linear_kernel(const float* __restrict__ x, int ldx, int m, int k,
                                                              const float* __restrict__ w,
                                                              const float* __restrict__ bias, int n,
                                                              float* __restrict__ y, int ldy) {
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    const int q = lane >> 4, r = lane & 15;
-    const int tok0 = blockIdx.x * (32 * TM) + (wid & 1) * (16 * TM);
-    const int ot0 = blockIdx.y * (2 * TN) + (wid >> 1) * TN;   // first output tile of this wave
-    const int ntile = n >> 4;
-    const float* xp[TM];
-    const float* wp[TN];
-#pragma unroll
-    for (int t = 0; t < TM; ++t) xp[t] = x + (size_t)min(tok0 + 16 * t + r, m - 1) * ldx + 4 * q;
-#pragma unroll
-    for (int u = 0; u < TN; ++u) wp[u] = w + (size_t)(16 * min(ot0 + u, ntile - 1) + r) * k + 4 * q;
-    f32x4 acc[TN][TM];
-#pragma unroll
-    for (int u = 0; u < TN; ++u)
-#pragma unroll
-        for (int t = 0; t < TM; ++t) acc[u][t] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const int KG = k >> 4;
-    f32x4 xa[TM], wa[TN];
-#pragma unroll
-    for (int t = 0; t < TM; ++t) xa[t] = ld4(xp[t]);
-#pragma unroll
-    for (int u = 0; u < TN; ++u) wa[u] = ld4(wp[u]);
-    for (int g = 0; g < KG; ++g) {
-        f32x4 xb[TM], wb[TN];
-        const int gn = (g + 1 < KG ? g + 1 : g) * 16;
-#pragma unroll
-        for (int t = 0; t < TM; ++t) xb[t] = ld4(xp[t] + gn);
-#pragma unroll
-        for (int u = 0; u < TN; ++u) wb[u] = ld4(wp[u] + gn);
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int u = 0; u < TN; ++u)
-#pragma unroll
-                for (int t = 0; t < TM; ++t) acc[u][t] = mfma4(wa[u][j], xa[t][j], acc[u][t]);
-#pragma unroll
-        for (int t = 0; t < TM; ++t) xa[t] = xb[t];
-#pragma unroll
-        for (int u = 0; u < TN; ++u) wa[u] = wb[u];
-    }
-#pragma unroll
-    for (int u = 0; u < TN; ++u) {
-        const int T = ot0 + u;
-        if (T >= ntile) continue;
-        const f32x4 bv = bias ? ld4(bias + 16 * T + 4 * q) : f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int t = 0; t < TM; ++t) {
-            const int tok = tok0 + 16 * t + r;
-            if (tok >= m) continue;
-            f32x4 v = acc[u][t] + bv;
+    gemm_nt_body<TM, TN>(x, ldx, m, w, k, n, k, [&](int o) {
+        const f32x4 bv = bias ? ld4(bias + o) : f32x4{0.f, 0.f, 0.f, 0.f};
+        return [=](int tok, f32x4 v) {
+            v += bv;
             if (ACT == 1) v = relu4(v);
             if (ACT == 2) v = f32x4{sigmoidf(v.x), sigmoidf(v.y), sigmoidf(v.z), sigmoidf(v.w)};
-            st4(y + (size_t)tok * ldy + 16 * T + 4 * q, v);
-        }
-    }
+            st4(y + (size_t)tok * ldy + o, v);
+        };
+    });
 }
 
 // LDS-tiled form for large token counts: a workgroup owns 128 tokens x (32 * WN) outputs, 4 waves as 2 x 2
@@ -202,14 +162,6 @@ static void launch_linear(const float* x, int ldx, int m, int k, const float* w,
     hipLaunchKernelGGL((linear_kernel<TM, TN, ACT>), grid, dim3(FUS_THREADS), 0, st, x, ldx, m, k, w, bias, n, y, ldy);
 }
 
-template <int TN>
-static void launch_linear_act(int act, const float* x, int ldx, int m, int k, const float* w, const float* bias, int n,
-                              float* y, int ldy, hipStream_t st) {
-    if (act == 0) launch_linear<TN, 0>(x, ldx, m, k, w, bias, n, y, ldy, st);
-    else if (act == 1) launch_linear<TN, 1>(x, ldx, m, k, w, bias, n, y, ldy, st);
-    else launch_linear<TN, 2>(x, ldx, m, k, w, bias, n, y, ldy, st);
-}
-
 extern "C" int gp_linear(const float* x, int ldx, int m, int k, const float* w, const float* bias, int n, int act,
                          float* y, int ldy, hipStream_t st) {
     GP_REQUIRE(x && w && y && m >= 0, "linear: null pointer");
@@ -221,27 +173,23 @@ extern "C" int gp_linear(const float* x, int ldx, int m, int k, const float* w, 
     if (!m) return GP_OK;
     if (m >= 1024 && k % LK_KC == 0 && n >= 64) {   // LDS-tiled: 128 tokens x 128 (or 64) outputs per workgroup
         const bool wide = n % 128 == 0;   // else 64-output columns (n = 96, 192, 288: less padding)
-#define GP_LIN_LDS(WN)                                                                                     \
-        if (act == 0) launch_linear_lds<WN, 0>(x, ldx, m, k, w, bias, n, y, ldy, st);                      \
-        else if (act == 1) launch_linear_lds<WN, 1>(x, ldx, m, k, w, bias, n, y, ldy, st);                 \
-        else launch_linear_lds<WN, 2>(x, ldx, m, k, w, bias, n, y, ldy, st);
-        if (wide) { GP_LIN_LDS(4) } else { GP_LIN_LDS(2) }
-#undef GP_LIN_LDS
+        with_act<3>(act, [&](auto A) {
+            if (wide) launch_linear_lds<4, A()>(x, ldx, m, k, w, bias, n, y, ldy, st);
+            else launch_linear_lds<2, A()>(x, ldx, m, k, w, bias, n, y, ldy, st);
+        });
         return gp_check_launch("linear_lds_kernel");
     }
     // few tokens (the GroupAll level's one token per object): 32 x 32 tiles, so that the grid still covers the
     // chip (m = 256, n = 1024: 256 workgroups instead of 32)
-    if ((long long)((m + 63) / 64) * ((n + 127) / 128) < 256 && n % 32 == 0) {
-        if (act == 0) launch_linear<1, 0, 1>(x, ldx, m, k, w, bias, n, y, ldy, st);
-        else if (act == 1) launch_linear<1, 1, 1>(x, ldx, m, k, w, bias, n, y, ldy, st);
-        else launch_linear<1, 2, 1>(x, ldx, m, k, w, bias, n, y, ldy, st);
-        return gp_check_launch("linear_kernel");
-    }
-    // output tiles per wave: the widest that divides n into whole workgroup columns
-    if (n % 128 == 0) launch_linear_act<4>(act, x, ldx, m, k, w, bias, n, y, ldy, st);
-    else if (n % 96 == 0) launch_linear_act<3>(act, x, ldx, m, k, w, bias, n, y, ldy, st);
-    else if (n % 64 == 0) launch_linear_act<2>(act, x, ldx, m, k, w, bias, n, y, ldy, st);
-    else launch_linear_act<1>(act, x, ldx, m, k, w, bias, n, y, ldy, st);
+    const bool few = (long long)((m + 63) / 64) * ((n + 127) / 128) < 256 && n % 32 == 0;
+    with_act<3>(act, [&](auto A) {
+        if (few) launch_linear<1, A(), 1>(x, ldx, m, k, w, bias, n, y, ldy, st);
+        // else output tiles per wave: the widest that divides n into whole workgroup columns
+        else if (n % 128 == 0) launch_linear<4, A()>(x, ldx, m, k, w, bias, n, y, ldy, st);
+        else if (n % 96 == 0) launch_linear<3, A()>(x, ldx, m, k, w, bias, n, y, ldy, st);
+        else if (n % 64 == 0) launch_linear<2, A()>(x, ldx, m, k, w, bias, n, y, ldy, st);
+        else launch_linear<1, A()>(x, ldx, m, k, w, bias, n, y, ldy, st);
+    });
     return gp_check_launch("linear_kernel");
 }
 
@@ -254,12 +202,6 @@ extern "C" int gp_linear(const float* x, int ldx, int m, int k, const float* w, 
 // LDS stages of one 32-deep chunk, one barrier per chunk. JT = 8 (WO = 4): every A fragment read from LDS
 // feeds 8 token tiles instead of 4, so the LDS traffic per MFMA drops by a third.
 constexpr int SL_THREADS = 512;
-#ifndef SL_DMA
-#define SL_DMA 1   // A planes global -> LDS by global_load_lds_dwordx4 (0: through registers and ds_write)
-#endif
-#ifndef SL_DIAG
-#define SL_DIAG 0     // timing diagnostics of linear_split_kernel's chunk loop (wrong results): see the loop
-#endif
 // 16 bytes per lane from global memory straight into LDS at lds + 16 * lane (lds wave-uniform)
 __device__ __forceinline__ void lds_dma16(const void* src, void* lds) {
     __builtin_amdgcn_global_load_lds(src, (__attribute__((address_space(3))) void*)lds, 16, 0, 0);
@@ -354,31 +296,19 @@ __global__ __launch_bounds__(SL_THREADS) void linear_split_kernel(SplitLinArgs a
             v1 = row[u] < a.m ? ld4(xr + 16) : f32x4{0.f, 0.f, 0.f, 0.f};
         }
     };
-    // A (the packed weight planes, stored as they are): SL_DMA copies them global -> LDS directly
+    // A (the packed weight planes, stored as they are) is copied global -> LDS directly
     // (global_load_lds_dwordx4: no registers, no ds_write; the wave's 64 lanes fill 1 KB at its LDS base)
-    auto load = [&](int c, int sdst, f32x4 (&ra)[WO], f32x4 (&rb)[2 * RU]) {
+    auto load = [&](int c, int sdst, f32x4 (&rb)[2 * RU]) {
 #pragma unroll
         for (int u = 0; u < WO; ++u) {
             const int idx = tid + SL_THREADS * u;
             const f16x8* src = W + ((size_t)(T0 + (idx >> 7)) * KC + c) * 128 + (idx & 127);
-#if SL_DMA
             lds_dma16(src, sA(sdst) + (idx & ~63));
-            (void)ra;
-#else
-            (void)sdst;
-            ra[u] = ld4(reinterpret_cast<const float*>(src));
-#endif
         }
 #pragma unroll
         for (int u = 0; u < RU; ++u) xload(c, u, rb[2 * u], rb[2 * u + 1]);
     };
-    auto store = [&](int s, const f32x4 (&ra)[WO], const f32x4 (&rb)[2 * RU]) {
-#if !SL_DMA
-#pragma unroll
-        for (int u = 0; u < WO; ++u) sA(s)[tid + SL_THREADS * u] = __builtin_bit_cast(f16x8, ra[u]);
-#else
-        (void)ra;
-#endif
+    auto store = [&](int s, const f32x4 (&rb)[2 * RU]) {
 #pragma unroll
         for (int u = 0; u < RU; ++u) {
 #pragma clang fp contract(off)
@@ -403,30 +333,14 @@ __global__ __launch_bounds__(SL_THREADS) void linear_split_kernel(SplitLinArgs a
     for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int j = 0; j < JT; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    f32x4 ra[WO], rb[2 * RU];
-    load(0, 0, ra, rb);
-    store(0, ra, rb);
-    if constexpr (SL_DMA) wait_all_mem();   // the direct-to-LDS copies have landed
+    f32x4 rb[2 * RU];
+    load(0, 0, rb);
+    store(0, rb);
+    wait_all_mem();   // the direct-to-LDS copies have landed
     __syncthreads();
     for (int c = 0; c < KC; ++c) {
         const int s = c & 1;
-#if SL_DIAG
-        // timing diagnostic (wrong results): bit 1 no x loads / split / B stores after chunk 0, bit 2 no weight
-        // copies after chunk 0, bit 4 no barrier wait on memory (the loop's vmcnt(0) dropped)
-        if (c + 1 < KC) {
-            if constexpr ((SL_DIAG & 2) == 0)
-#pragma unroll
-                for (int u = 0; u < WO; ++u) {
-                    const int idx = tid + SL_THREADS * u;
-                    lds_dma16(W + ((size_t)(T0 + (idx >> 7)) * KC + c + 1) * 128 + (idx & 127), sA(s ^ 1) + (idx & ~63));
-                }
-            if constexpr ((SL_DIAG & 1) == 0)
-#pragma unroll
-                for (int u = 0; u < RU; ++u) xload(c + 1, u, rb[2 * u], rb[2 * u + 1]);
-        }
-#else
-        if (c + 1 < KC) load(c + 1, s ^ 1, ra, rb);
-#endif
+        if (c + 1 < KC) load(c + 1, s ^ 1, rb);
         if constexpr (JT == 4) {
             f16x8 bh[JT], bl[JT];
 #pragma unroll
@@ -476,15 +390,9 @@ __global__ __launch_bounds__(SL_THREADS) void linear_split_kernel(SplitLinArgs a
                     for (int j = 0; j < 2; ++j) acc[i][j0 + j] = mfma_h(ah[i], bh[j], acc[i][j0 + j]);
             }
         }
-#if SL_DIAG
-        if ((SL_DIAG & 1) == 0 && c + 1 < KC) store(s ^ 1, ra, rb);
-        if constexpr ((SL_DIAG & 4) == 0) wait_all_mem();
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-#else
-        if (c + 1 < KC) store(s ^ 1, ra, rb);
-        if constexpr (SL_DMA) wait_all_mem();
+        if (c + 1 < KC) store(s ^ 1, rb);
+        wait_all_mem();
         __syncthreads();
-#endif
     }
     // epilogue: unscale (exact powers of two), bias, activation; the accumulator of tile (i, j) holds outputs
     // 4q..4q+3 of output tile T0 + 4 wo + i for token (JT wt + j) * 16 + nn
@@ -530,15 +438,19 @@ __global__ __launch_bounds__(SL_THREADS) void linear_split_kernel(SplitLinArgs a
     }
 }
 
-// 256-token workgroups (JT = 8) when they still give the chip at least two workgroups per CU; GENPOSE2_LSPLIT_JT=4
-// keeps the 128-token tiles (tuning)
-#ifndef SL_JT8_DEFAULT
-#define SL_JT8_DEFAULT 1
-#endif
-static bool sl_wide_tokens(int m, int npad) {
-    const char* env = getenv("GENPOSE2_LSPLIT_JT");
-    const bool on = env ? env[0] == '8' : SL_JT8_DEFAULT != 0;
-    return on && (long long)((m + 255) / 256) * (npad / 256) >= 512;
+// 256-token workgroups (JT = 8) when they still give the chip at least two workgroups per CU
+static bool sl_wide_tokens(int m, int npad) { return (long long)((m + 255) / 256) * (npad / 256) >= 512; }
+
+template <int WO, int ACT, int JT, int IM = 0>
+static void launch_linear_split(const SplitLinArgs& a, int npad, hipStream_t st) {
+    constexpr int BM = 16 * JT * (8 / WO);
+    const dim3 grid(npad / (64 * WO), (a.m + BM - 1) / BM);
+    hipLaunchKernelGGL((linear_split_kernel<WO, ACT, JT, IM>), grid, dim3(SL_THREADS), (sl_lds_bytes<WO, JT>()), st, a);
+}
+
+int gp_rowmax_abs(const float* x, int ldx, int m, int k, float* rmax, hipStream_t st) {
+    hipLaunchKernelGGL(fus_rowmax_kernel, dim3((m + 3) / 4), dim3(256), 0, st, x, ldx, m, k, rmax);
+    return gp_check_launch("fus_rowmax_kernel");
 }
 
 extern "C" size_t gp_linear_split_words(int n, int k) {
@@ -558,30 +470,16 @@ extern "C" int gp_linear_split(const float* x, int ldx, int m, int k, const int3
                "linear_split: pointers must be 16-byte aligned");
     GP_REQUIRE(act != 3 || k == 2 * n, "linear_split: the gate mix (act 3) takes x = [cur | att], k = 2n (k=%d n=%d)", k, n);
     if (!m) return GP_OK;
-    if (!(flags & GP_LINEAR_RMAX_GIVEN)) {
-        hipLaunchKernelGGL(fus_rowmax_kernel, dim3((m + 3) / 4), dim3(256), 0, st, x, ldx, m, k, rmax);
-        FUS_TRY(gp_check_launch("fus_rowmax_kernel"));
-    }
+    if (!(flags & GP_LINEAR_RMAX_GIVEN)) GP_TRY(gp_rowmax_abs(x, ldx, m, k, rmax, st));
     if (ymax && hipMemsetAsync(ymax, 0, sizeof(float) * (size_t)m, st) != hipSuccess)
         return gp_check_launch("linear_split ymax memset");
     SplitLinArgs a{x, ldx, m, k, rmax, wpk, bias, n, y, ldy, reinterpret_cast<unsigned*>(ymax), 0, 0};
     const int npad = (n + 127) / 128 * 128;
-#define GP_LSPLIT(WO, JT)                                                                                          \
-    {                                                                                                          \
-        constexpr int BM = 16 * JT * (8 / WO);                                                                 \
-        const dim3 grid(npad / (64 * WO), (m + BM - 1) / BM);                                                  \
-        constexpr size_t lds = sl_lds_bytes<WO, JT>();                                                         \
-        if (act == 0) hipLaunchKernelGGL((linear_split_kernel<WO, 0, JT>), grid, dim3(SL_THREADS), lds, st, a); \
-        else if (act == 1) hipLaunchKernelGGL((linear_split_kernel<WO, 1, JT>), grid, dim3(SL_THREADS), lds, st, a); \
-        else if (act == 2) hipLaunchKernelGGL((linear_split_kernel<WO, 2, JT>), grid, dim3(SL_THREADS), lds, st, a); \
-        else if (act == 3) hipLaunchKernelGGL((linear_split_kernel<WO, 3, JT>), grid, dim3(SL_THREADS), lds, st, a); \
-        else if (act == 4) hipLaunchKernelGGL((linear_split_kernel<WO, 4, JT>), grid, dim3(SL_THREADS), lds, st, a); \
-        else hipLaunchKernelGGL((linear_split_kernel<WO, 5, JT>), grid, dim3(SL_THREADS), lds, st, a); \
-    }
-    if (npad % 256 == 0 && sl_wide_tokens(m, npad)) GP_LSPLIT(4, 8)
-    else if (npad % 256 == 0) GP_LSPLIT(4, 4)
-    else GP_LSPLIT(2, 4)
-#undef GP_LSPLIT
+    with_act<6>(act, [&](auto A) {
+        if (npad % 256 == 0 && sl_wide_tokens(m, npad)) launch_linear_split<4, A(), 8>(a, npad, st);
+        else if (npad % 256 == 0) launch_linear_split<4, A(), 4>(a, npad, st);
+        else launch_linear_split<2, A(), 4>(a, npad, st);
+    });
     return gp_check_launch("linear_split_kernel");
 }
 
@@ -599,16 +497,8 @@ int gp_linear_split_conv3x3(const float* f, int b, int g, int d, const int32_t* 
     if (!m) return GP_OK;
     SplitLinArgs a{f, d, m, k, rmax, wpk, bias, n, y, n, nullptr, g, d / 32};
     const int npad = (n + 127) / 128 * 128;
-#define GP_LSPLIT_IM(WO)                                                                                       \
-    {                                                                                                          \
-        constexpr int BM = 16 * 4 * (8 / WO);                                                                  \
-        const dim3 grid(npad / (64 * WO), (m + BM - 1) / BM);                                                  \
-        constexpr size_t lds = sl_lds_bytes<WO, 4>();                                                          \
-        hipLaunchKernelGGL((linear_split_kernel<WO, 1, 4, 1>), grid, dim3(SL_THREADS), lds, st, a);            \
-    }
-    if (npad % 256 == 0) GP_LSPLIT_IM(4)
-    else GP_LSPLIT_IM(2)
-#undef GP_LSPLIT_IM
+    if (npad % 256 == 0) launch_linear_split<4, 1, 4, 1>(a, npad, st);
+    else launch_linear_split<2, 1, 4, 1>(a, npad, st);
     return gp_check_launch("linear_split_kernel<im2col>");
 }
 
@@ -1269,11 +1159,11 @@ extern "C" int gp_fusion_attend(const float* cur, const float* ot, int b, int n,
     float* ca = hid + fus_align(B * (c / 2));
     float* tstat = ca + fus_align(B * c);
     hipLaunchKernelGGL(fusion_colmean_kernel, dim3((2 * c + 63) / 64, b), dim3(FUS_THREADS), 0, st, cur, ot, n, c, colmean);
-    FUS_TRY(gp_check_launch("fusion_colmean_kernel"));
+    GP_TRY(gp_check_launch("fusion_colmean_kernel"));
     hipLaunchKernelGGL(fusion_tokstat_kernel, dim3((n + 3) / 4, b), dim3(FUS_THREADS), 0, st, cur, n, c, tstat);
-    FUS_TRY(gp_check_launch("fusion_tokstat_kernel"));
-    FUS_TRY(gp_linear(colmean, 2 * c, b, 2 * c, ca1_w, ca1_b, c / 2, 1, hid, c / 2, st));
-    FUS_TRY(gp_linear(hid, c / 2, b, c / 2, ca3_w, ca3_b, c, 2, ca, c, st));
+    GP_TRY(gp_check_launch("fusion_tokstat_kernel"));
+    GP_TRY(gp_linear(colmean, 2 * c, b, 2 * c, ca1_w, ca1_b, c / 2, 1, hid, c / 2, st));
+    GP_TRY(gp_linear(hid, c / 2, b, c / 2, ca3_w, ca3_b, c, 2, ca, c, st));
     hipLaunchKernelGGL(fusion_gcat_kernel, dim3((n + 3) / 4, b), dim3(FUS_THREADS), 0, st, cur, ot, n, c, ca, tstat, sp_w,
                        gcat, gmax);
     return gp_check_launch("fusion_gcat_kernel");

@@ -12,6 +12,7 @@
 //                     S x (the host-built position table) and the row softmax between them, a wave per row;
 //   final mix         (F + relu(geo_w) O) + relu(edge_w) (F x edge[c % (d/4)]), in the reference's order.
 #include "gp_common.h"
+#include "gp_gemm_nt.h"   // gemm_nt_body
 
 constexpr int IE_THREADS = 256;
 
@@ -73,22 +74,9 @@ __global__ __launch_bounds__(IE_THREADS) void imgenc_im2col_kernel(const float* 
     }
 }
 
-// Row maxima of the implicit im2col (gp_linear_split_conv3x3): pmax[t] = max |f[t][:]| per pixel (a wave per pixel),
+// Row maxima of the implicit im2col (gp_linear_split_conv3x3): pmax[t] = max |f[t][:]| per pixel (gp_rowmax_abs),
 // then rmax[t] = the max of pmax over the pixel's in-grid 3x3 neighbourhood -- the max |x| of its im2col row (the
 // zero padding adds 0), bit for bit what a row max over the formed column buffer gives.
-__global__ __launch_bounds__(IE_THREADS) void imgenc_pixel_max_kernel(const float* __restrict__ f, int t, int d,
-                                                                      float* __restrict__ pmax) {
-    const int r = blockIdx.x * (IE_THREADS / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (r >= t) return;
-    float v = 0.f;
-    for (int c = 4 * lane; c < d; c += 256) {
-        const f32x4 x = ld4(f + (size_t)r * d + c);
-        v = fmaxf(v, fmaxf(fmaxf(fabsf(x.x), fabsf(x.y)), fmaxf(fabsf(x.z), fabsf(x.w))));
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-    if (lane == 0) pmax[r] = v;
-}
 __global__ void imgenc_nbr_max_kernel(const float* __restrict__ pmax, int t, int g, float* __restrict__ rmax) {
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= t) return;
@@ -127,69 +115,18 @@ __global__ void imgenc_pool_kernel(const float* __restrict__ y, int nb, int np, 
 }
 
 // ---------------------------------------------------------------- batched GEMM (exact f32 MFMA)
-// C[z][i][j] = sum_k A[z][i][k] B[z][j][k]; A rows i (lda, batch stride sa), B rows j (ldb, sb), C (ldc, sc).
-// 4 waves as 2 (i) x 2 (j); a wave owns TM i-tiles x TN j-tiles of 16. Lane (q, r) feeds float4 k-slices
-// 16g + 4q .. +3 of row r of both operands (k a multiple of 16, rows 16-byte aligned).
+// C[z][i][j] = sum_k A[z][i][k] B[z][j][k]; A rows i (lda, batch stride sa), B rows j (ldb, sb), C (ldc, sc):
+// gemm_nt_body per batch z = block z, storing its sums as they are (K a multiple of 16, rows 16-byte aligned).
 template <int TM, int TN>
 __global__ __launch_bounds__(IE_THREADS) void bgemm_nt_kernel(const float* __restrict__ A, int lda, long long sa,
                                                               const float* __restrict__ Bm, int ldb, long long sb,
                                                               float* __restrict__ C, int ldc, long long sc, int M,
                                                               int N, int K) {
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    const int q = lane >> 4, r = lane & 15;
     const int z = blockIdx.z;
-    A += z * sa;
-    Bm += z * sb;
     C += z * sc;
-    const int i0 = blockIdx.x * (32 * TM) + (wid & 1) * (16 * TM);
-    const int j0 = blockIdx.y * (32 * TN) + (wid >> 1) * (16 * TN);
-    const float* ap[TM];
-    const float* bp[TN];
-#pragma unroll
-    for (int t = 0; t < TM; ++t) ap[t] = A + (size_t)min(i0 + 16 * t + r, M - 1) * lda + 4 * q;
-#pragma unroll
-    for (int u = 0; u < TN; ++u) bp[u] = Bm + (size_t)min(j0 + 16 * u + r, N - 1) * ldb + 4 * q;
-    f32x4 acc[TN][TM];
-#pragma unroll
-    for (int u = 0; u < TN; ++u)
-#pragma unroll
-        for (int t = 0; t < TM; ++t) acc[u][t] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const int KG = K >> 4;
-    f32x4 aa[TM], ba[TN];
-#pragma unroll
-    for (int t = 0; t < TM; ++t) aa[t] = ld4(ap[t]);
-#pragma unroll
-    for (int u = 0; u < TN; ++u) ba[u] = ld4(bp[u]);
-    for (int g = 0; g < KG; ++g) {
-        f32x4 an[TM], bn[TN];
-        const int kn = (g + 1 < KG ? g + 1 : g) * 16;
-#pragma unroll
-        for (int t = 0; t < TM; ++t) an[t] = ld4(ap[t] + kn);
-#pragma unroll
-        for (int u = 0; u < TN; ++u) bn[u] = ld4(bp[u] + kn);
-        // D rows = j (B operand rows as the MFMA A input), columns = i
-#pragma unroll
-        for (int jj = 0; jj < 4; ++jj)
-#pragma unroll
-            for (int u = 0; u < TN; ++u)
-#pragma unroll
-                for (int t = 0; t < TM; ++t) acc[u][t] = mfma4(ba[u][jj], aa[t][jj], acc[u][t]);
-#pragma unroll
-        for (int t = 0; t < TM; ++t) aa[t] = an[t];
-#pragma unroll
-        for (int u = 0; u < TN; ++u) ba[u] = bn[u];
-    }
-#pragma unroll
-    for (int u = 0; u < TN; ++u) {
-        const int jt = j0 + 16 * u;
-        if (jt >= N) continue;
-#pragma unroll
-        for (int t = 0; t < TM; ++t) {
-            const int i = i0 + 16 * t + r;
-            if (i >= M) continue;
-            st4(C + (size_t)i * ldc + jt + 4 * q, acc[u][t]);
-        }
-    }
+    gemm_nt_body<TM, TN>(A + z * sa, lda, M, Bm + z * sb, ldb, N, K, [&](int j) {
+        return [=](int i, f32x4 v) { st4(C + (size_t)i * ldc + j, v); };
+    });
 }
 
 static void launch_bgemm_nt(const float* A, int lda, long long sa, const float* B, int ldb, long long sb, float* C,
@@ -374,50 +311,46 @@ static int img_encoder_impl(const float* l0, const float* l1, const float* l2, i
     float* edge = edge_out ? edge_out : reinterpret_cast<float*>(ws + L.edge);
     float* rmax = reinterpret_cast<float*>(ws + L.rmax);
     const int T = b * np, hid = d / 2, co = d / 4;
-    int rc;
     // 1. layer attention: Linear(d, d/2) + ReLU over each layer's tokens, then the fuse kernel
     const float* layers[3] = {l0, l1, l2};
     for (int l = 0; l < 3; ++l)
-        if ((rc = img_linear_relu(layers[l], T, d, la_w1, la_w1_h, la_b1, hid, h + (size_t)l * T * hid, rmax, st)))
-            return rc;
+        GP_TRY(img_linear_relu(layers[l], T, d, la_w1, la_w1_h, la_b1, hid, h + (size_t)l * T * hid, rmax, st));
     hipLaunchKernelGGL(imgenc_layer_fuse_kernel, dim3((T + 3) / 4), dim3(IE_THREADS), 0, st, (const float*)h, hid,
                        la_w2, la_b2, l0, l1, l2, T, d, fused, layer_w);
-    if ((rc = gp_check_launch("imgenc_layer_fuse_kernel"))) return rc;
+    GP_TRY(gp_check_launch("imgenc_layer_fuse_kernel"));
     // 2. edge branch: im2col GEMM + ReLU per chunk of objects, then the pixel mean
     if (implicit) {   // the split GEMM gathers its column rows from the feature map itself
         float* pmax = col;   // (b * np) pixel maxima in the implicit layout
-        hipLaunchKernelGGL(imgenc_pixel_max_kernel, dim3((T + 3) / 4), dim3(IE_THREADS), 0, st, (const float*)fused, T, d,
-                           pmax);
-        if ((rc = gp_check_launch("imgenc_pixel_max_kernel"))) return rc;
+        GP_TRY(gp_rowmax_abs(fused, d, T, d, pmax, st));
         hipLaunchKernelGGL(imgenc_nbr_max_kernel, dim3((T + 255) / 256), dim3(256), 0, st, (const float*)pmax, T, g,
                            rmax);
-        if ((rc = gp_check_launch("imgenc_nbr_max_kernel"))) return rc;
-        if ((rc = gp_linear_split_conv3x3(fused, b, g, d, conv_w_h, conv_b, co, ey, rmax, st))) return rc;
+        GP_TRY(gp_check_launch("imgenc_nbr_max_kernel"));
+        GP_TRY(gp_linear_split_conv3x3(fused, b, g, d, conv_w_h, conv_b, co, ey, rmax, st));
         hipLaunchKernelGGL(imgenc_pool_kernel, dim3((b * co + 255) / 256), dim3(256), 0, st, (const float*)ey, b, np, co,
                            edge);
-        if ((rc = gp_check_launch("imgenc_pool_kernel"))) return rc;
+        GP_TRY(gp_check_launch("imgenc_pool_kernel"));
     }
     for (int c0 = 0; c0 < (implicit ? 0 : b); c0 += IE_EDGE_CHUNK) {
         const int nb = b - c0 < IE_EDGE_CHUNK ? b - c0 : IE_EDGE_CHUNK;
         hipLaunchKernelGGL(imgenc_im2col_kernel, dim3(nb * np), dim3(IE_THREADS), 0, st,
                            (const float*)(fused + (size_t)c0 * np * d), np, g, d, col);
-        if ((rc = gp_check_launch("imgenc_im2col_kernel"))) return rc;
-        if ((rc = img_linear_relu(col, nb * np, 9 * d, conv_w, conv_w_h, conv_b, co, ey, rmax, st))) return rc;
+        GP_TRY(gp_check_launch("imgenc_im2col_kernel"));
+        GP_TRY(img_linear_relu(col, nb * np, 9 * d, conv_w, conv_w_h, conv_b, co, ey, rmax, st));
         hipLaunchKernelGGL(imgenc_pool_kernel, dim3((nb * co + 255) / 256), dim3(256), 0, st, (const float*)ey, nb, np,
                            co, edge + (size_t)c0 * co);
-        if ((rc = gp_check_launch("imgenc_pool_kernel"))) return rc;
+        GP_TRY(gp_check_launch("imgenc_pool_kernel"));
     }
     // 3. geometric attention: S = G G^T, softmax(S x table), O = P F
     launch_bgemm_nt(fused + co, d, (long long)np * d, fused + co, d, (long long)np * d, s, np, (long long)np * np, np,
                     np, d - co, b, st);
-    if ((rc = gp_check_launch("bgemm_nt_kernel<scores>"))) return rc;
+    GP_TRY(gp_check_launch("bgemm_nt_kernel<scores>"));
     hipLaunchKernelGGL(imgenc_softmax_kernel, dim3((T + 3) / 4), dim3(IE_THREADS), 0, st, s, geo_table, T, np);
-    if ((rc = gp_check_launch("imgenc_softmax_kernel"))) return rc;
+    GP_TRY(gp_check_launch("imgenc_softmax_kernel"));
     hipLaunchKernelGGL(imgenc_transpose_kernel, dim3((np + 31) / 32, (d + 31) / 32, b), dim3(IE_THREADS), 0, st,
                        (const float*)fused, np, d, ft);
-    if ((rc = gp_check_launch("imgenc_transpose_kernel"))) return rc;
+    GP_TRY(gp_check_launch("imgenc_transpose_kernel"));
     launch_bgemm_nt(s, np, (long long)np * np, ft, np, (long long)np * d, o, d, (long long)np * d, np, d, np, b, st);
-    if ((rc = gp_check_launch("bgemm_nt_kernel<values>"))) return rc;
+    GP_TRY(gp_check_launch("bgemm_nt_kernel<values>"));
     // 4. final mix
     const long long n = (long long)T * d;
     hipLaunchKernelGGL(imgenc_combine_kernel, dim3((unsigned)((n + IE_THREADS - 1) / IE_THREADS)), dim3(IE_THREADS), 0,

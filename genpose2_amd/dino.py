@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from . import _lib, arch, weights
-from ._lib import check
+from ._lib import check, vp
 from .device import require_device_tensor, stream_handle
 from .fus_encoder import pack_split_linear
 
@@ -74,10 +74,6 @@ def pack_dino(sd: weights.StateDict) -> Dict[str, np.ndarray]:
     return out
 
 
-def _vp(t: Optional[torch.Tensor]):
-    return ctypes.c_void_p(None if t is None else t.data_ptr())
-
-
 class DinoBackbone:
     """dinov3_vits16plus on device. ``get_intermediate_layers`` as the reference calls it; ``calls`` counts its
     invocations."""
@@ -117,7 +113,7 @@ class DinoBackbone:
             tab = torch.empty((hp * wp, 64), dtype=torch.float32, device=self.device)
             per = None if self.periods is None else np.ascontiguousarray(self.periods, np.float32)
             check(self.lib.gp_dino_rope_table(None if per is None else per.ctypes.data_as(ctypes.c_void_p), hp, wp,
-                                              _vp(tab), ctypes.c_void_p(stream_handle(self.device))), "dino_rope_table")
+                                              vp(tab), ctypes.c_void_p(stream_handle(self.device))), "dino_rope_table")
             self._rope[(hp, wp)] = tab
         return tab
 
@@ -174,8 +170,8 @@ class DinoBackbone:
         wts = self._weights(rope, hp, wp)
         lay = (ctypes.c_int * len(layers))(*layers)
         ptrs = (ctypes.c_void_p * len(layers))(*[o.data_ptr() for o in outs])
-        check(self.lib.gp_dino_forward(ctypes.byref(wts), _vp(x), B, H, W, len(layers), lay, ptrs, ARITH[self.arith],
-                                       _vp(ws), ws.numel(), ctypes.c_void_p(stream_handle(self.device))),
+        check(self.lib.gp_dino_forward(ctypes.byref(wts), vp(x), B, H, W, len(layers), lay, ptrs, ARITH[self.arith],
+                                       vp(ws), ws.numel(), ctypes.c_void_p(stream_handle(self.device))),
               "dino_forward")
         self.calls += 1
         return tuple(outs)

@@ -29,14 +29,10 @@ import numpy as np
 import torch
 
 from . import _lib, arch, pack, weights
-from ._lib import check
+from ._lib import check, vp
 from .device import EncoderGeometry, require_device_tensor, stream_handle
 
 _ACT = {"none": 0, "relu": 1, "sigmoid": 2, "gate_mix": 3}   # gate_mix: gp_linear_split only
-
-
-def _vp(t: Optional[torch.Tensor]):
-    return ctypes.c_void_p(None if t is None else t.data_ptr())
 
 
 def pack_relpe(sd: weights.StateDict, prefix: str) -> np.ndarray:
@@ -124,7 +120,6 @@ class FusEncoderModel:
         self._fws: Optional[torch.Tensor] = None
         self._rmax: Optional[torch.Tensor] = None
         self._gen = 0   # bumped whenever this model writes geometry into its workspace
-        self.fused_bias = os.environ.get("GENPOSE2_FUSED_RELPE", "1") == "1"
         self.set_arith(os.environ.get("GENPOSE2_ENC_ARITH", "split_f16"))
 
     @property
@@ -169,10 +164,10 @@ class FusEncoderModel:
                 if self._rmax is None or self._rmax.numel() < m:
                     self._rmax = torch.empty(m, dtype=torch.float32, device=self.device)
                 rmax = self._rmax
-            check(self.lib.gp_linear_split(_vp(x), k, m, k, _vp(self.t[f"{w}.wh"]), _vp(b), n, _ACT[act], _vp(y), n,
-                                           _vp(rmax), flags, _vp(ymax), self._s()), f"linear_split {w}")
+            check(self.lib.gp_linear_split(vp(x), k, m, k, vp(self.t[f"{w}.wh"]), vp(b), n, _ACT[act], vp(y), n,
+                                           vp(rmax), flags, vp(ymax), self._s()), f"linear_split {w}")
         else:
-            check(self.lib.gp_linear(_vp(x), k, m, k, _vp(W), _vp(b), n, _ACT[act], _vp(y), n, self._s()),
+            check(self.lib.gp_linear(vp(x), k, m, k, vp(W), vp(b), n, _ACT[act], vp(y), n, self._s()),
                   f"linear {w}")
         return y
 
@@ -182,8 +177,8 @@ class FusEncoderModel:
     def add_ln(self, x: torch.Tensor, r: torch.Tensor, name: str, ymax: Optional[torch.Tensor] = None) -> torch.Tensor:
         d = x.shape[-1]
         y = torch.empty_like(x)
-        check(self.lib.gp_add_layernorm(_vp(x), _vp(r), x.numel() // d, d, _vp(self.t[f"{name}.w"]),
-                                        _vp(self.t[f"{name}.b"]), ctypes.c_float(arch.LN_EPS), _vp(y), _vp(ymax),
+        check(self.lib.gp_add_layernorm(vp(x), vp(r), x.numel() // d, d, vp(self.t[f"{name}.w"]),
+                                        vp(self.t[f"{name}.b"]), ctypes.c_float(arch.LN_EPS), vp(y), vp(ymax),
                                         self._s()), f"add_layernorm {name}")
         return y
 
@@ -198,7 +193,7 @@ class FusEncoderModel:
             # output is v itself -- only the wv rows of the fused QKV are evaluated
             W, bq = self.t[f"tf{lv}.qkv.w"][2 * d:], self.t[f"tf{lv}.qkv.b"][2 * d:]
             att = torch.empty_like(x)
-            check(self.lib.gp_linear(_vp(x), d, B, d, _vp(W), _vp(bq), d, 0, _vp(att), d, self._s()), "linear wv")
+            check(self.lib.gp_linear(vp(x), d, B, d, vp(W), vp(bq), d, 0, vp(att), d, self._s()), "linear wv")
             amax = None
         else:
             amax = self._rowmax_buf(B * n, self.split_linear(f"tf{lv}.wo", B * n))
@@ -218,20 +213,20 @@ class FusEncoderModel:
         qkv = self.linear(x, f"tf{lv}.qkv")
         att = torch.empty_like(x)
         if xyz is None:
-            check(self.lib.gp_mha_attention(_vp(qkv), None, B, n, d, _vp(att), _vp(amax), self._s()), "mha_attention")
-        elif d // arch.FUS_HEADS <= 16 and self.fused_bias:
+            check(self.lib.gp_mha_attention(vp(qkv), None, B, n, d, vp(att), vp(amax), self._s()), "mha_attention")
+        elif d // arch.FUS_HEADS <= 16:
             # level 0: the bias evaluated in the attention kernel's registers (no (B, 8, n, n) buffer, 2.1 GB
             # at B=256); at level 1 (head dim 32) the kernel holds one wave per SIMD and the two-kernel path
             # is faster (0.45 vs 0.73 ms)
-            check(self.lib.gp_mha_relpe_attention(_vp(qkv), _vp(xyz), _vp(self.t[f"pe{lv}"]), B, n, d, _vp(att),
-                                                  _vp(amax), self._s()), "mha_relpe_attention")
+            check(self.lib.gp_mha_relpe_attention(vp(qkv), vp(xyz), vp(self.t[f"pe{lv}"]), B, n, d, vp(att),
+                                                  vp(amax), self._s()), "mha_relpe_attention")
         else:
             need = int(self.lib.gp_relpe_bias_bytes(B, n)) // 4
             if self._bias is None or self._bias.numel() < need:
                 self._bias = torch.empty(need, dtype=torch.float32, device=self.device)
-            check(self.lib.gp_relpe_bias(_vp(self.t[f"pe{lv}"]), _vp(xyz), B, n, _vp(self._bias), self._s()),
+            check(self.lib.gp_relpe_bias(vp(self.t[f"pe{lv}"]), vp(xyz), B, n, vp(self._bias), self._s()),
                   "relpe_bias")
-            check(self.lib.gp_mha_attention(_vp(qkv), _vp(self._bias), B, n, d, _vp(att), _vp(amax), self._s()),
+            check(self.lib.gp_mha_attention(vp(qkv), vp(self._bias), B, n, d, vp(att), vp(amax), self._s()),
                   "mha_attention")
         return att
 
@@ -247,9 +242,9 @@ class FusEncoderModel:
         if self._fws is None or self._fws.numel() < need:
             self._fws = torch.empty(need, dtype=torch.uint8, device=self.device)
         gmax = self._rowmax_buf(B * n, self.split_linear(f"fu{k}.gate", B * n))
-        check(self.lib.gp_fusion_attend(_vp(cur), _vp(ot), B, n, c, _vp(t[f"fu{k}.ca1.w"]), _vp(t[f"fu{k}.ca1.b"]),
-                                        _vp(t[f"fu{k}.ca3.w"]), _vp(t[f"fu{k}.ca3.b"]), _vp(t[f"fu{k}.sp.w"]),
-                                        _vp(gcat), _vp(gmax), _vp(self._fws), self._fws.numel(), self._s()),
+        check(self.lib.gp_fusion_attend(vp(cur), vp(ot), B, n, c, vp(t[f"fu{k}.ca1.w"]), vp(t[f"fu{k}.ca1.b"]),
+                                        vp(t[f"fu{k}.ca3.w"]), vp(t[f"fu{k}.ca3.b"]), vp(t[f"fu{k}.sp.w"]),
+                                        vp(gcat), vp(gmax), vp(self._fws), self._fws.numel(), self._s()),
               "fusion_attend")
         if self.split_linear(f"fu{k}.gate", B * n):   # the gate linear's epilogue does the mix
             fmax = self._rowmax_buf(B * n, self.split_linear(f"fu{k}.output_conv", B * n))
@@ -257,13 +252,13 @@ class FusEncoderModel:
             return self.linear(fused, f"fu{k}.output_conv", "relu", rmax=fmax)
         g = self.linear(gcat, f"fu{k}.gate", "sigmoid")
         fused = torch.empty_like(cur)
-        check(self.lib.gp_fusion_mix(_vp(g), _vp(gcat), B * n, c, _vp(fused), self._s()), "fusion_mix")
+        check(self.lib.gp_fusion_mix(vp(g), vp(gcat), B * n, c, vp(fused), self._s()), "fusion_mix")
         return self.linear(fused, f"fu{k}.output_conv", "relu")
 
     def interp(self, x: torch.Tensor, n_out: int, ymax: Optional[torch.Tensor] = None) -> torch.Tensor:
         B, n_in, c = x.shape
         y = torch.empty((B, n_out, c), dtype=torch.float32, device=self.device)
-        check(self.lib.gp_interp_points(_vp(x), B, n_in, c, n_out, _vp(y), _vp(ymax), self._s()), "interp_points")
+        check(self.lib.gp_interp_points(vp(x), B, n_in, c, n_out, vp(y), vp(ymax), self._s()), "interp_points")
         return y
 
     # ------------------------------------------------------------ forward
@@ -286,7 +281,7 @@ class FusEncoderModel:
         ws = self.workspace(B, N)
         self._gen += 1
         cur = torch.cuda.current_stream(self.device)
-        check(self.lib.gp_encoder_geometry(_vp(pts), B, N, _vp(ws), ws.numel(), ctypes.c_void_p(cur.cuda_stream)),
+        check(self.lib.gp_encoder_geometry(vp(pts), B, N, vp(ws), ws.numel(), ctypes.c_void_p(cur.cuda_stream)),
               "encoder_geometry")
         ev = torch.cuda.Event()
         ev.record(cur)
@@ -307,7 +302,7 @@ class FusEncoderModel:
         ws = self.workspace(B, N)
         if geometry is None:
             self._gen += 1   # the self-contained pass rewrites the geometry in this workspace
-            check(self.lib.gp_encoder_fps(_vp(pts), B, N, _vp(ws), ws.numel(), self._s()), "encoder_fps")
+            check(self.lib.gp_encoder_fps(vp(pts), B, N, vp(ws), ws.numel(), self._s()), "encoder_fps")
             geo = None
         else:
             if geometry.key != key:
@@ -336,13 +331,13 @@ class FusEncoderModel:
             cout = arch.level_out_channels(lv)
             sa = torch.empty((B, m, cout), dtype=torch.float32, device=self.device)
             if geo is None:
-                check(self.lib.gp_sa_level(_vp(self.wbuf), self.offsets.ctypes.data_as(_lib.c_int64_p), lv,
-                                           feats.shape[2], _vp(pts), B, N, _vp(feats), _vp(ws), ws.numel(), _vp(sa),
+                check(self.lib.gp_sa_level(vp(self.wbuf), self.offsets.ctypes.data_as(_lib.c_int64_p), lv,
+                                           feats.shape[2], vp(pts), B, N, vp(feats), vp(ws), ws.numel(), vp(sa),
                                            self._s()), f"sa_level {lv}")
             else:
-                check(self.lib.gp_sa_level_geom(_vp(self.wbuf), self.offsets.ctypes.data_as(_lib.c_int64_p), lv,
-                                                feats.shape[2], _vp(pts), B, N, _vp(feats), _vp(geo), _vp(ws),
-                                                ws.numel(), _vp(sa), self._s()), f"sa_level_geom {lv}")
+                check(self.lib.gp_sa_level_geom(vp(self.wbuf), self.offsets.ctypes.data_as(_lib.c_int64_p), lv,
+                                                feats.shape[2], vp(pts), B, N, vp(feats), vp(geo), vp(ws),
+                                                ws.numel(), vp(sa), self._s()), f"sa_level_geom {lv}")
             gsrc = ws if geo is None else geo
             xyz = gsrc[off[lv * 5 + 1]:].view(torch.float32)[: B * m * 3].view(B, m, 3) if lv < 4 else None
             feats = self.transformer(lv, sa, xyz)

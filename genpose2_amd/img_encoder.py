@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from . import _lib, arch, weights
-from ._lib import check
+from ._lib import check, vp
 from .device import require_device_tensor, stream_handle
 
 
@@ -57,10 +57,6 @@ def pack_img_scalars(sd: weights.StateDict, prefix: str = "img_encoder") -> np.n
     v = [float(np.asarray(sd[f"{prefix}.layer_attn.2.bias"]).reshape(-1)[0]),
          max(float(sd[f"{prefix}.geo_weight"]), 0.0), max(float(sd[f"{prefix}.edge_weight"]), 0.0)]
     return np.array(v, np.float32)
-
-
-def _vp(t: Optional[torch.Tensor]):
-    return ctypes.c_void_p(None if t is None else t.data_ptr())
 
 
 class ImgEncoderModel:
@@ -100,23 +96,20 @@ class ImgEncoderModel:
         if any(tuple(v.shape) != (B, n, d) for v in ls):
             raise ValueError("the three DINOv3 layers must have one shape (B, np, d)")
         split = self.arith == "split_f16"
-        # the edge conv's split GEMM with implicit im2col (gp_img_encoder3), or over a formed column buffer
-        # (gp_img_encoder2, GENPOSE2_IMG_IMPLICIT=0: same products, another summation order)
-        implicit = os.environ.get("GENPOSE2_IMG_IMPLICIT", "1")[:1] != "0"
-        need = int(self.lib.gp_img_encoder3_workspace_size(B, n, d, int(split)) if implicit
-                   else self.lib.gp_img_encoder_workspace_size(B, n, d))
+        # the edge conv's split GEMM runs with implicit im2col (gp_img_encoder3); gp_img_encoder2 forms a column
+        # buffer instead (same products, another summation order) and is the tests' reference
+        need = int(self.lib.gp_img_encoder3_workspace_size(B, n, d, int(split)))
         if self._ws is None or self._ws.numel() < need:
             self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
         out = torch.empty((B, n, d), dtype=torch.float32, device=self.device)
         lw = torch.empty((B, n, 3), dtype=torch.float32, device=self.device) if return_parts else None
         edge = torch.empty((B, d // 4), dtype=torch.float32, device=self.device) if return_parts else None
         b2, gg, eg = (float(v) for v in self.scalars)
-        fn = self.lib.gp_img_encoder3 if implicit else self.lib.gp_img_encoder2
-        conv_h = self.t["conv_w_hp" if implicit else "conv_w_h"]
-        check(fn(_vp(ls[0]), _vp(ls[1]), _vp(ls[2]), B, n, d, _vp(self.t["la_w1"]), _vp(self.t["la_b1"]),
-                 _vp(self.t["la_w2"]), b2, _vp(self.t["geo_table"]), _vp(self.t["conv_w"]), _vp(self.t["conv_b"]), gg,
-                 eg, _vp(self.t["la_w1_h"] if split else None), _vp(conv_h if split else None), _vp(out), _vp(lw),
-                 _vp(edge), _vp(self._ws), self._ws.numel(), self._s()), "img_encoder")
+        check(self.lib.gp_img_encoder3(
+            vp(ls[0]), vp(ls[1]), vp(ls[2]), B, n, d, vp(self.t["la_w1"]), vp(self.t["la_b1"]), vp(self.t["la_w2"]),
+            b2, vp(self.t["geo_table"]), vp(self.t["conv_w"]), vp(self.t["conv_b"]), gg, eg,
+            vp(self.t["la_w1_h"] if split else None), vp(self.t["conv_w_hp"] if split else None), vp(out), vp(lw),
+            vp(edge), vp(self._ws), self._ws.numel(), self._s()), "img_encoder")
         if return_parts:
             return out, {"layer_w": lw, "edge": edge}
         return out
@@ -133,6 +126,6 @@ class ImgEncoderModel:
             raise ValueError(f"roi_xs / roi_ys must both be (B={B}, N), got {tuple(xs.shape)} / {tuple(ys.shape)}")
         N = xs.shape[1]
         out = torch.empty((B, N, d), dtype=torch.float32, device=self.device)
-        check(self.lib.gp_gather_patch_points(_vp(feat), B, n, d, _vp(xs), _vp(ys), N, arch.IMG_PATCH_PX,
-                                              arch.IMG_GRID, _vp(out), self._s()), "gather_patch_points")
+        check(self.lib.gp_gather_patch_points(vp(feat), B, n, d, vp(xs), vp(ys), N, arch.IMG_PATCH_PX,
+                                              arch.IMG_GRID, vp(out), self._s()), "gather_patch_points")
         return out

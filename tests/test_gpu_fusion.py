@@ -297,7 +297,10 @@ def test_relpe_bias_vs_oracle(lib, fus_sd, n):
 
 
 @pytest.mark.parametrize("n,d,with_bias", [(512, 96, True), (256, 256, True), (128, 512, True), (64, 1024, True),
-                                           (1, 1024, False), (77, 256, True)])
+                                           (1, 1024, False), (77, 256, True),
+                                           # three 32-key LDS chunks (the last of 13 keys) under an unaligned bias
+                                           # row; no bias with n % 4 != 0; four 64-key chunks, the last one tile
+                                           (77, 1024, True), (70, 96, False), (200, 512, False)])
 def test_mha_attention_vs_torch(lib, n, d, with_bias):
     from genpose2_amd._lib import check
     B, H = 2, 8
