@@ -107,6 +107,7 @@ _SIGS: Dict[str, tuple] = {
                                     c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_uint64,
                                     c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "gp_debug_q8_probe": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "gp_debug_pose_tail_f32": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "gp_debug_ode_obj_rec_size": (c_size_t, []),
     "gp_debug_ode_obj_control": (c_int, [ctypes.POINTER(HeadWeights), c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                          c_int, c_double, c_double, c_int, c_int, c_void_p, c_void_p, c_void_p,

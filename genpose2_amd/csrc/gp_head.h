@@ -1205,7 +1205,11 @@ template <>
 __device__ __forceinline__ double tsqrt<double>(double v) { return sqrt(v); }
 
 // normalize_rotation(.., 'rot_matrix') (misc.py:327-344): rotation_6d_to_matrix GS with
-// F.normalize's eps 1e-12 (rotation_conversions.py:571-575).
+// F.normalize's eps 1e-12 (rotation_conversions.py:571-575). The bits are those of the written-out order below,
+// which tests/pose_ref.py states operation by operation and oracle.gram_schmidt reproduces -- not torch's: F.normalize's
+// vector_norm sums the three squares in another order, and the reference's float32 CPU result differs from this
+// one in the last place on 23 % of rows (43 % after the quaternion; tests/test_cpu_pose_edges.py). The clamp is a
+// select, so a NaN norm becomes 1e-12 where torch's clamp_min keeps the NaN (the quaternion is NaN either way).
 template <typename T>
 __device__ __forceinline__ void gram_schmidt6(T* v) {
 #pragma clang fp contract(off)
@@ -1226,7 +1230,8 @@ __device__ __forceinline__ void gram_schmidt6(T* v) {
 
 // gram_schmidt6 spread over the four lanes of a row (lane part p: 0 -> v[0:3], 1 -> v[3:6],
 // 2 -> translation, untouched; 3 idle). Same operations and order as gram_schmidt6<float>: IEEE division
-// and square root on purpose (the hardware's approximate ones would not give the reference's bits).
+// and square root on purpose (the hardware's approximate ones would not give the bits of the written-out order
+// that tests/pose_ref.py states and the oracle reproduces; tests/test_gpu_pose_edges.py holds both forms to them).
 __device__ __forceinline__ void gram_schmidt6_quad(float* v, int p, int lane) {
 #pragma clang fp contract(off)
     float n1 = sqrtf((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]);

@@ -354,7 +354,7 @@ __device__ __forceinline__ void pc_update_rows(const PCArgs& a, int i, const PCS
                                                int* obj, int g, int lane, int r0, float gacc, float (&x3)[3],
                                                const float (&sv)[3], const float (&z1v)[3], const float (&z2v)[3],
                                                const SplitScalars& hs, bool store_x, int trace_slot) {
-#pragma clang fp contract(off)   // and IEEE division / square root on purpose: the chain gives the reference's bits
+#pragma clang fp contract(off)   // and IEEE division / square root on purpose: the chain gives the oracle's bits
     constexpr bool SPLIT = PL != 0;
     const int p = lane & 3;
     const int e0 = 3 * (p < 3 ? p : 0);
@@ -969,4 +969,61 @@ extern "C" int gp_debug_q8_probe(const uint16_t* f16_bits, int n, int plane, uin
     hipLaunchKernelGGL(q8_probe_kernel<false>, dim3(nwg), dim3(HT), 0, stream, f16_bits, n, plane, q8);
     hipLaunchKernelGGL(q8_probe_kernel<true>, dim3(nwg), dim3(HT), 0, stream, f16_bits, n, plane, q8_via_f32);
     return gp_check_launch("q8_probe_kernel");
+}
+
+// ============================================================================ fp32 pose tail probe
+// The last step's tail of pc_update_rows on caller-given rows, in that kernel's lane layout: a wave holds 16 rows,
+// four lanes per row, part p < 3 owns elements [3p, 3p+3), p == 2 adds the centre of object r / kper; then
+// gram_schmidt6_quad, res, the row gathered through LDS and quat_from_gs<float> on the p == 0 lane. The device
+// functions are the kernel's own. Lanes of rows past `rows` compute on the last row (they take part in the quad
+// broadcast); only their stores are masked.
+__global__ __launch_bounds__(64) void pose_tail_f32_kernel(const float* __restrict__ mean_in, int rows, int kper,
+                                                           const float* center, float* __restrict__ res,
+                                                           float* __restrict__ q) {
+#pragma clang fp contract(off)
+    __shared__ float xu[16 * 9];
+    const int lane = threadIdx.x;
+    const int p = lane & 3, c = lane >> 2;
+    const int e0 = 3 * (p < 3 ? p : 0);
+    const int r = blockIdx.x * 16 + c;
+    const bool live = r < rows;
+    const int rr = live ? r : rows - 1;
+    float mean[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) mean[k] = ld1(mean_in + (size_t)rr * 9 + e0 + k);   // no 12-byte load (gp_common.h)
+    if (p == 2) {
+        const float* cp = center + (size_t)(rr / kper) * 3;
+        mean[0] += ld1(cp);
+        mean[1] += ld1(cp + 1);
+        mean[2] += ld1(cp + 2);
+    }
+    gram_schmidt6_quad(mean, p, lane);
+    if (live && p < 3) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            res[(size_t)r * 9 + e0 + k] = mean[k];
+            xu[c * 9 + e0 + k] = mean[k];
+        }
+    }
+    wave_sync();
+    if (p == 0 && live) {
+        float m9[9], qq[4];
+#pragma unroll
+        for (int j = 0; j < 9; ++j) m9[j] = xu[c * 9 + j];
+        quat_from_gs<float>(m9, qq);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) q[(size_t)r * 7 + j] = qq[j];
+        q[(size_t)r * 7 + 4] = m9[6];
+        q[(size_t)r * 7 + 5] = m9[7];
+        q[(size_t)r * 7 + 6] = m9[8];
+    }
+}
+
+extern "C" int gp_debug_pose_tail_f32(const float* mean, int rows, int k, const float* pts_center, float* res,
+                                      float* q, hipStream_t stream) {
+    GP_REQUIRE(mean && pts_center && res && q && rows >= 0 && k >= 1, "debug_pose_tail_f32: bad arguments");
+    if (!rows) return GP_OK;
+    hipLaunchKernelGGL(pose_tail_f32_kernel, dim3((rows + 15) / 16), dim3(64), 0, stream, mean, rows, k, pts_center,
+                       res, q);
+    return gp_check_launch("pose_tail_f32_kernel");
 }

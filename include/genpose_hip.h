@@ -281,6 +281,13 @@ int gp_energy_score_eval(const gp_head_weights *w, const gp_head_grad_weights *g
 int gp_debug_q8_probe(const uint16_t *f16_bits, int n, int plane, uint8_t *q8, uint8_t *q8_via_f32,
                       hipStream_t stream);
 
+/* Test aid for the fp32 pose tail of the PC step: the last step's tail of gp_pc_sample's update waves on
+ * caller-given rows, in their lane layout (16 rows per wave, four lanes per row) and through their device
+ * functions: mean (R,9) fp32 -> res (R,9) = [GS of [:6], [6:] + pts_center[r / k]] and q (R,7) = [quaternion wxyz
+ * of res, res[6:]]. All DEVICE pointers; mean is not written; pts_center holds ceil(rows / k) centres. */
+int gp_debug_pose_tail_f32(const float *mean, int rows, int k, const float *pts_center, float *res, float *q,
+                           hipStream_t stream);
+
 /* Test aid for the per-object RK45 controller (gp_ode_sample_object): one launch of its control kernel as the
  * sampler launches it for attempt n, on caller-owned DEVICE buffers. It decides attempt n - 1 of every object from
  * rowsq (nobj * kper: per row, the sum over its 9 entries of (err/scale)^2; read when decide != 0) and prepares

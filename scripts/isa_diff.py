@@ -32,6 +32,8 @@ def kernels(so):
                 code = re.sub(r"<[^>]*>", "", line.split("//")[0]).strip()
                 if code and code != "...":   # "...": zero padding up to the next symbol's alignment
                     ins.append(code)
+            while ins and ins[-1] == "s_nop 0":   # padding after s_endpgm: its length depends on what follows
+                ins.pop()
             out[fn] = ins
     return out
 
