@@ -11,7 +11,9 @@
 // words and their poll. What differs is the stage: like_obj_attempt_kernel carries the JVP trunk of
 // like_stage_kernel (NP primal column tiles and their NP tangent tiles; the tangent columns see no pobj / tproj
 // term), the state is scipy's flat [x (9 R) | logp (R)] of the call's R rows, and a row's error sum covers its ten
-// entries in entry order (nine x, then logp). These kernels have a translation unit of their own so that they
+// entries in entry order (nine x, then logp). The attempt kernel's row-record prologue (ode_obj_rows_to_lds), the
+// workspace's state block (ode_state_layout) and the common stage arguments (ode_obj_args) are gp_ode.h's, shared
+// with gp_ode_sample_object. These kernels have a translation unit of their own so that they
 // cannot move the register assignment of the kernels that were there before them.
 #include <cstddef>
 
@@ -58,24 +60,8 @@ __global__ __launch_bounds__(EVAL_WV * 64) void like_obj_attempt_kernel(LikeObjA
     const int tid = threadIdx.x;
     const int r0 = blockIdx.x * ROWS;
     const size_t n9 = (size_t)a.rows * 9;
-    int act = 0;
-    if (tid < ROWS) {
-        const int o = obj_of_row(r0 + tid, a.rows, a.kper);
-        const OdeObjRec* rc = a.rec + o;
-        act = (r0 + tid < a.rows) && rc->active != 0;
-        obj[tid] = o;
-        obj[ROWS + tid] = o;
-        ract[tid] = act;
-        rpend[tid] = rc->pend;
-        rh[tid] = rc->h;
-    } else if (tid < ROWS + 36) {
-        tab[tid - ROWS] = a.single ? 1.0 : tb.A[tid - ROWS];
-    } else if (tid < ROWS + 42) {
-        tab[tid - ROWS] = tb.B[tid - ROWS - 36];
-    } else if (tid < ROWS + 42 + ODE_NK) {
-        kin[tid - ROWS - 42] = a.k[tid - ROWS - 42];
-    }
-    if (!__syncthreads_or(act)) return;   // none of this workgroup's objects runs
+    // none of this workgroup's objects runs: done
+    if (!ode_obj_rows_to_lds<ROWS, true>(a, tb, r0, obj, ract, rpend, rh, tab, kin)) return;
     if (!a.single) {
         // the accepted step of the objects that go on: y_new -> y, K_6 -> K_0 (these rows are this workgroup's in
         // every attempt; the first stage's barrier orders the stores before the stages' loads)
@@ -216,17 +202,14 @@ __global__ __launch_bounds__(256) void like_obj_final_kernel(LikeObjFinalArgs a)
 
 namespace {
 struct LikeObjLayout {
-    size_t y, ynew, k[ODE_NK], f1, dlogp, total;
+    OdeStateBlock st;
+    size_t dlogp, total;
     OdeObjTail tail;
 };
 LikeObjLayout like_obj_layout(int rows, int nobj) {
     LikeObjLayout L = {};
-    const size_t vec = align256((size_t)rows * 10 * sizeof(double));
     size_t off = 0;
-    L.y = off; off += vec;
-    L.ynew = off; off += vec;
-    for (int j = 0; j < ODE_NK; ++j) { L.k[j] = off; off += vec; }
-    L.f1 = off; off += vec;
+    L.st = ode_state_layout(off, rows, 10);
     L.dlogp = off; off += align256((size_t)rows * sizeof(double));
     L.tail = ode_obj_tail_layout(off, rows, nobj);
     L.total = off;
@@ -242,24 +225,8 @@ int like_obj_np(const gp_head_weights* w, int rows_total) {
 LikeObjArgs like_obj_args(const gp_head_weights* w, const float* init, const float* zrow, const float* eps, double* y,
                           double* ynew, double* const* kslots, double* f1, double* rowsq, double rtol, double atol,
                           int rows, int k) {
-    LikeObjArgs a = {};
-    a.w = *w;
-    a.init = init;
-    a.zrow = zrow;
+    LikeObjArgs a = ode_obj_args<LikeObjArgs>(w, init, zrow, y, ynew, kslots, f1, rowsq, rtol, atol, rows, k);
     a.eps = eps;
-    a.y = y;
-    a.ynew = ynew;
-    for (int j = 0; j < ODE_NK; ++j) {
-        a.k[j] = kslots[j];
-        a.e[j] = kE7[j];
-    }
-    a.f1 = f1;
-    a.rowsq = rowsq;
-    a.rtol = rtol;
-    a.atol = atol;
-    a.rows = rows;
-    a.kper = k;
-    a.nobj = rows / k;
     return a;
 }
 
@@ -300,9 +267,9 @@ extern "C" int gp_like_sample_object(const gp_head_weights* w, const float* pobj
     const long long n9 = (long long)rows * 9, n = (long long)rows * 10;
     const int np = like_obj_np(w, rows_total);   // the whole batch's tile class
     double* K[ODE_NK];
-    for (int j = 0; j < ODE_NK; ++j) K[j] = dptr(L.k[j]);
-    LikeObjArgs a = like_obj_args(w, sv.init, sv.zrow, eps_dir, dptr(L.y), dptr(L.ynew), K, dptr(L.f1), sv.rowsq, rtol,
-                                  atol, rows, k);
+    for (int j = 0; j < ODE_NK; ++j) K[j] = dptr(L.st.k[j]);
+    LikeObjArgs a = like_obj_args(w, sv.init, sv.zrow, eps_dir, dptr(L.st.y), dptr(L.st.ynew), K, dptr(L.st.f1),
+                                  sv.rowsq, rtol, atol, rows, k);
     const OdeTableau tb = ode_tableau();
     auto stages = [&](const OdeObjRec* r, int single) {
         a.rec = r;

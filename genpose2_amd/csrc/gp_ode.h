@@ -7,6 +7,13 @@
 // between "the state is in y" and "the final records are on the host" is one host driver (ode_obj_solve, defined in
 // gp_ode.hip) that gp_ode_sample_object and gp_like_sample_object both call with their stage launch, and the
 // select_initial_step scalars, the init-norms kernel, the tableau and the status reads are defined once, here.
+// So is the host plumbing around a stage launch, which every entry calls with its own stage launcher: one
+// right-hand side (ode_rhs_once), the stages 1..6 of an attempt (ode_run_stages; ode_attempt_host around it for the
+// host-controlled entries), the final denoise's arguments and scalars (ode_denoise_begin, ode_denoise_scalars), the
+// state block of a whole-solve workspace (ode_state_layout), the per-object stage arguments (ode_obj_args) and the
+// copy the host waits for (ode_copy_sync). On the device the two fused attempt kernels share ode_attempt_to_lds and
+// the two per-object attempt kernels ode_obj_rows_to_lds; the stage bodies stay four, one per translation unit's
+// trunk (the files' headers say why).
 #pragma once
 #include <cmath>
 #include <cstdlib>
@@ -107,6 +114,17 @@ struct OdeTableau {
     double A[36], B[6];
 };
 
+// The tableau and the K slots of a fused attempt (ode_attempt_kernel, ode_energy_attempt_kernel) into LDS: read per
+// use (wave-uniform), not held in registers across the six stages. tab: 42 doubles (A, then B); the caller's
+// barrier follows.
+__device__ __forceinline__ void ode_attempt_to_lds(const OdeStageArgs& a, const OdeCtl* c, const OdeTableau& tb,
+                                                   double* tab, const double** kin) {
+    const int tid = threadIdx.x;
+    if (tid < 36) tab[tid] = tb.A[tid];
+    else if (tid < 42) tab[tid] = tb.B[tid - 36];
+    else if (tid < 42 + ODE_NK) kin[tid - 42] = a.kbuf[c->kidx[tid - 42]];
+}
+
 // Final denoise (samplers.py:240-249) + epilogue: the arguments of ode_denoise_kernel
 struct OdeDenoiseArgs {
     gp_head_weights w;
@@ -156,6 +174,35 @@ __device__ __forceinline__ double ode_obj_wave_sum(int n, F v) {
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) t += __shfl_xor(t, off, 64);
     return t;
+}
+
+// The prologue of a per-object attempt kernel (ode_obj_attempt_kernel, like_obj_attempt_kernel; Args: OdeObjArgs or
+// LikeObjArgs), one thread per row of the tile, tableau entry and K slot: the row's object (TANGENT: again at
+// obj[ROWS + row], for the likelihood's tangent columns), active / pending flags and step from its record, the tableau
+// (all ones for a single evaluation) and the K slots into LDS. Returns whether any row of the workgroup runs (a
+// barrier).
+template <int ROWS, bool TANGENT, typename Args>
+__device__ __forceinline__ int ode_obj_rows_to_lds(const Args& a, const OdeTableau& tb, int r0, int* obj, int* ract,
+                                                   int* rpend, double* rh, double* tab, const double** kin) {
+    const int tid = threadIdx.x;
+    int act = 0;
+    if (tid < ROWS) {
+        const int o = obj_of_row(r0 + tid, a.rows, a.kper);
+        const OdeObjRec* rc = a.rec + o;
+        act = (r0 + tid < a.rows) && rc->active != 0;
+        obj[tid] = o;
+        if (TANGENT) obj[ROWS + tid] = o;
+        ract[tid] = act;
+        rpend[tid] = rc->pend;
+        rh[tid] = rc->h;
+    } else if (tid < ROWS + 36) {
+        tab[tid - ROWS] = a.single ? 1.0 : tb.A[tid - ROWS];
+    } else if (tid < ROWS + 42) {
+        tab[tid - ROWS] = tb.B[tid - ROWS - 36];
+    } else if (tid < ROWS + 42 + ODE_NK) {
+        kin[tid - ROWS - 42] = a.k[tid - ROWS - 42];
+    }
+    return __syncthreads_or(act);
 }
 
 // select_initial_step norms of every object (scipy _ivp/common.py) over its kper rows of NE entries, one wave per
@@ -253,6 +300,42 @@ static inline double ode_init_h_abs(double h0, double d1, double d2_raw, double 
 
 static inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
+// The state block every whole-solve workspace starts with: y, y_new, K_0..K_6 and f1 (the Euler probe's
+// derivative), each a 256-aligned vector of rows * entries doubles; byte offsets from the base
+struct OdeStateBlock {
+    size_t y, ynew, k[ODE_NK], f1;
+};
+static inline OdeStateBlock ode_state_layout(size_t& off, int rows, int entries) {
+    OdeStateBlock S = {};
+    const size_t vec = align256((size_t)rows * (size_t)entries * sizeof(double));
+    S.y = off; off += vec;
+    S.ynew = off; off += vec;
+    for (int j = 0; j < ODE_NK; ++j) { S.k[j] = off; off += vec; }
+    S.f1 = off; off += vec;
+    return S;
+}
+
+// A copy the host waits for (the whole-solve entries' norm reads and record uploads): `who`: `what` on failure
+static inline int ode_copy_sync(void* dst, const void* src, size_t bytes, hipMemcpyKind kind, hipStream_t stream,
+                                const char* who, const char* what) {
+    GP_REQUIRE(hipMemcpyAsync(dst, src, bytes, kind, stream) == hipSuccess &&
+                   hipStreamSynchronize(stream) == hipSuccess, "%s: %s", who, what);
+    return GP_OK;
+}
+
+// The final denoise's scalars of eps (samplers.py:240-249): g is formed from a float32 1-element tensor, so sigma
+// and g^2 are float32 products; the step is a float64 quotient rounded once
+struct OdeDenoiseScalars {
+    float te, sig, g2, step;
+};
+static inline OdeDenoiseScalars ode_denoise_scalars(double eps, int steps) {
+    const float te = (float)eps;
+    const float sig = sigma32(te);
+    const float g = sig * (float)diff_scale();
+    const float step = (float)((1.0 - eps) / (steps > 0 ? steps : 1000));
+    return {te, sig, g * g, step};
+}
+
 // Host resources of gp_ode_sample's status reads (a pinned int and an event on the stream's device),
 // leased from a per-device pool for one call and returned after it. A per-thread cache bound them to
 // the first device a thread used, which breaks a host that drives several GPUs from one thread (or a
@@ -330,6 +413,103 @@ int ode_launch_times(const gp_head_weights* w, const float* t32, int nt, void* w
 int ode_launch_norm(const double* part, int n, double count, double* out, hipStream_t stream);
 // Byte offset of the error partials in a host-controlled workspace (behind the 6 time rows)
 size_t ode_part_offset();
+
+// One right-hand side for gp_ode_rhs, gp_like_rhs and gp_ode_rhs_energy (`who`: the entry's name in messages; its
+// own extra checks come first, in the entry): the common checks, the stage arguments, the time row of t32 and
+// launch(args), the entry's stage launch, which returns a status.
+template <typename Launch>
+static inline int ode_rhs_once(const char* who, const gp_head_weights* w, const float* pobj, float t32, float sigma,
+                               double coef, const double* y, const double* const* kin, const double* acoef, int nk,
+                               double h, int rows, int k, double* kout, void* workspace, size_t workspace_bytes,
+                               hipStream_t stream, Launch launch) {
+    GP_REQUIRE(w && pobj && y && kout && workspace && rows >= 1 && k >= 1, "%s: bad arguments", who);
+    GP_REQUIRE(nk >= 0 && nk < ODE_NK && (nk == 0 || (kin && acoef)), "%s: nk must be in [0, 6]", who);
+    GP_REQUIRE(workspace_bytes >= gp_ode_workspace_size(rows), "%s: workspace too small", who);
+    OdeStageArgs a = {};
+    a.w = *w;
+    a.pobj = pobj;
+    a.tproj = static_cast<const float*>(workspace);
+    a.sigma = sigma;
+    a.coef = coef;
+    a.y = y;
+    for (int j = 0; j < nk; ++j) {
+        GP_REQUIRE(kin[j] != nullptr, "%s: null stage pointer", who);
+        a.k[j] = kin[j];
+        a.a[j] = acoef[j];
+    }
+    a.nk = nk;
+    a.h = h;
+    a.kout = kout;
+    a.rows = rows;
+    a.kper = k;
+    GP_TRY(ode_launch_times(w, &t32, 1, workspace, stream));
+    return launch(a);
+}
+
+// Stages 1..6 of one attempt, in stream order: K_s = f(t + c_s h, y + (sum_{j<s} A[s][j] K_j) h) for s = 1..5
+// (tableau_a: 6x6 row-major), then y_new = y + (sum_{j<6} B_j K_j) h, K_6 = f(t + h, y_new) and the error partials.
+// set(a, s): the stage's own fields (the host's time row, sigma, coef and K slot, or only a.stage where the
+// controller's record supplies them); launch(a, last): the entry's stage launch, which returns a status.
+template <typename Set, typename Launch>
+static inline int ode_run_stages(OdeStageArgs& a, const double* tableau_a, const double* b, const double* e,
+                                 double* ynew, double* part, Set set, Launch launch) {
+    for (int s = 1; s < 6; ++s) {
+        set(a, s);
+        a.nk = s;
+        for (int j = 0; j < s; ++j) a.a[j] = tableau_a[s * 6 + j];
+        GP_TRY(launch(a, false));
+    }
+    set(a, 6);
+    a.nk = 6;
+    for (int j = 0; j < 6; ++j) a.a[j] = b[j];
+    for (int j = 0; j < ODE_NK; ++j) a.e[j] = e[j];
+    a.ynew = ynew;
+    a.part = part;
+    return launch(a, true);
+}
+
+// One host-controlled attempt for gp_ode_attempt, gp_like_attempt and gp_ode_attempt_energy (`who` as above): the
+// common checks, the six time rows, ode_run_stages with the host's scalars and launch(args, last), and the RMS norm
+// of the nwg() error partials (the entry's tiling, asked for behind the checks) over `count` elements into err_out.
+template <typename Nwg, typename Launch>
+static inline int ode_attempt_host(const char* who, const gp_head_weights* w, const float* pobj, const float* t32_6,
+                                   const float* sigma_6, const double* coef_6, const double* y, double* const* kslots,
+                                   const double* tableau_a, const double* b, const double* e, double h, double rtol,
+                                   double atol, int rows, int k, double* ynew, double* err_out, void* workspace,
+                                   size_t workspace_bytes, hipStream_t stream, Nwg nwg, double count, Launch launch) {
+    GP_REQUIRE(w && pobj && t32_6 && sigma_6 && coef_6 && y && kslots && tableau_a && b && e && ynew && err_out &&
+                   workspace && rows >= 1 && k >= 1,
+               "%s: bad arguments", who);
+    GP_REQUIRE(workspace_bytes >= gp_ode_workspace_size(rows), "%s: workspace too small", who);
+    for (int j = 0; j < ODE_NK; ++j) GP_REQUIRE(kslots[j] != nullptr, "%s: null K slot", who);
+    const float* tproj = static_cast<const float*>(workspace);
+    double* part = reinterpret_cast<double*>(static_cast<char*>(workspace) + ode_part_offset());
+    GP_TRY(ode_launch_times(w, t32_6, 6, workspace, stream));
+    OdeStageArgs a = {};
+    a.w = *w;
+    a.pobj = pobj;
+    a.y = y;
+    a.h = h;
+    a.rows = rows;
+    a.kper = k;
+    a.rtol = rtol;
+    a.atol = atol;
+    for (int j = 0; j < ODE_NK; ++j) a.k[j] = kslots[j];
+    auto set = [&](OdeStageArgs& s, int st) {
+        s.tproj = tproj + (size_t)(st - 1) * 768;
+        s.sigma = sigma_6[st - 1];
+        s.coef = coef_6[st - 1];
+        s.kout = kslots[st];
+    };
+    GP_TRY(ode_run_stages(a, tableau_a, b, e, ynew, part, set, launch));
+    return ode_launch_norm(part, nwg(), count, err_out, stream);
+}
+
+// The final denoise's common part for gp_ode_denoise / gp_ode_sample_object and gp_ode_denoise_energy: the common
+// checks, the time row of t32 and the kernel's arguments into *a
+int ode_denoise_begin(const char* who, const gp_head_weights* w, const float* pobj, float t32, float sigma, float g2,
+                      float step, const double* x, int rows, int k, const float* pts_center, double* pose, double* q,
+                      void* workspace, size_t workspace_bytes, hipStream_t stream, OdeDenoiseArgs* a);
 // One launch of ode_obj_control_kernel (the per-object controller: decides attempt n - 1 from the rows' error sums,
 // prepares attempt n and its ns folded time rows), as gp_ode_sample_object launches it
 int ode_obj_launch_control(const gp_head_weights* w, const float* pobj, const OdeObjRec* cin, OdeObjRec* cout,
@@ -352,6 +532,32 @@ static inline OdeObjTail ode_obj_tail_layout(size_t& off, int rows, int nobj) {
     T.count = off; off += 256;
     T.dstat = off; off += 256;
     return T;
+}
+
+// What the per-object stage arguments share (OdeObjArgs, gp_ode.hip; LikeObjArgs, gp_like_object.hip: the same
+// fields and eps), but for the records and `single`. f1: null where only attempts run
+template <typename Args>
+static inline Args ode_obj_args(const gp_head_weights* w, const float* init, const float* zrow, double* y, double* ynew,
+                                double* const* kslots, double* f1, double* rowsq, double rtol, double atol, int rows,
+                                int k) {
+    Args a = {};
+    a.w = *w;
+    a.init = init;
+    a.zrow = zrow;
+    a.y = y;
+    a.ynew = ynew;
+    for (int j = 0; j < ODE_NK; ++j) {
+        a.k[j] = kslots[j];
+        a.e[j] = kE7[j];
+    }
+    a.f1 = f1;
+    a.rowsq = rowsq;
+    a.rtol = rtol;
+    a.atol = atol;
+    a.rows = rows;
+    a.kper = k;
+    a.nobj = rows / k;
+    return a;
 }
 
 // One per-object solve (ode_obj_solve): nobj objects of k rows with `entries` state entries per row

@@ -11,7 +11,9 @@
 // controller's scalars stay on the host (genpose2_amd/ode.py): one 8-byte read per attempt. The
 // device-controlled attempts (gp_ode_auto_attempt) run all six stages of an attempt in one launch
 // (ode_attempt_kernel); the host-controlled ones launch each stage (ode_stage_kernel). What the energy agent's
-// stages (gp_ode_energy.hip) share with these is declared in gp_ode.h.
+// stages (gp_ode_energy.hip) and the per-object likelihood (gp_like_object.hip) share with these is in gp_ode.h:
+// the entries here hand ode_rhs_once, ode_attempt_host and ode_run_stages their stage launch (ode_launch_stage,
+// like_launch_stage) and keep only their own checks.
 #include <chrono>
 #include <cstddef>
 #include <cstdlib>
@@ -122,16 +124,11 @@ __global__ __launch_bounds__(EVAL_WV * 64) void ode_attempt_kernel(OdeStageArgs 
     __shared__ HeadSmem<NT, EVAL_WV, PL> sm;
     __shared__ int obj[ROWS];
     __shared__ double y0s[ROWS * 9], y1s[ROWS * 9], esq[NTH];
-    // the tableau and the K slots of this attempt in LDS: read per use (wave-uniform), not held in registers
-    // across the six stages
     __shared__ double tab[42];
     __shared__ const double* kin[ODE_NK];
     const OdeCtl* c = a.ctl;
     if (!c->active) return;
-    const int tid = threadIdx.x;
-    if (tid < 36) tab[tid] = tb.A[tid];
-    else if (tid < 42) tab[tid] = tb.B[tid - 36];
-    else if (tid < 42 + ODE_NK) kin[tid - 42] = a.kbuf[c->kidx[tid - 42]];
+    ode_attempt_to_lds(a, c, tb, tab, kin);
     const double* y = a.ybuf[c->yi];
     const double h = c->h;
     __syncthreads();
@@ -149,14 +146,18 @@ __global__ __launch_bounds__(EVAL_WV * 64) void ode_attempt_kernel(OdeStageArgs 
                               const_cast<double*>(kin[6]), a.ybuf[c->yi ^ 1], sm, obj, y0s, y1s, esq, hs);
 }
 
-// Stage-kernel launch of `nt` column tiles per workgroup (1 for the exact-fp32 trunk).
-template <int MODE>
-static void ode_launch_stage(const OdeStageArgs& a, int nt, hipStream_t st) {
+// Stage-kernel launch of `nt` column tiles per workgroup (1 for the exact-fp32 trunk); last: MODE 1. what: the
+// launch check's label, or null where the caller checks once behind a later launch (stages 1..5 of an attempt).
+static int ode_launch_stage(const OdeStageArgs& a, int nt, bool last, const char* what, hipStream_t st) {
     const int nwg = (a.rows + 16 * nt - 1) / (16 * nt);
     const dim3 grid(nwg), blk(EVAL_WV * 64);
     head_dispatch(a.w.pe2_h ? X3P : 0, nt, [&](auto pl, auto ntc) {
-        hipLaunchKernelGGL((ode_stage_kernel<MODE, pl.value, ntc.value>), grid, blk, 0, st, a);
+        if (last)
+            hipLaunchKernelGGL((ode_stage_kernel<1, pl.value, ntc.value>), grid, blk, 0, st, a);
+        else
+            hipLaunchKernelGGL((ode_stage_kernel<0, pl.value, ntc.value>), grid, blk, 0, st, a);
     });
+    return what ? gp_check_launch(what) : GP_OK;
 }
 
 static int ode_nt(const gp_head_weights* w, int rows) { return head_pick_nt(rows, w->pe2_h != nullptr); }
@@ -257,12 +258,16 @@ static int like_np(const gp_head_weights* w, int rows) {
     return (w->pe2_h != nullptr && rows >= PC_SPLIT_NT2_MIN) ? 2 : 1;
 }
 
-template <int MODE>
-static void like_launch_stage(const OdeStageArgs& a, const float* eps, int np, hipStream_t st) {
+static int like_launch_stage(const OdeStageArgs& a, const float* eps, int np, bool last, const char* what,
+                             hipStream_t st) {
     const dim3 grid((a.rows + 16 * np - 1) / (16 * np)), blk(EVAL_WV * 64);
     head_dispatch<2>(a.w.pe2_h ? X3P : 0, np, [&](auto pl, auto npc) {
-        hipLaunchKernelGGL((like_stage_kernel<MODE, pl.value, npc.value>), grid, blk, 0, st, a, eps);
+        if (last)
+            hipLaunchKernelGGL((like_stage_kernel<1, pl.value, npc.value>), grid, blk, 0, st, a, eps);
+        else
+            hipLaunchKernelGGL((like_stage_kernel<0, pl.value, npc.value>), grid, blk, 0, st, a, eps);
     });
+    return what ? gp_check_launch(what) : GP_OK;
 }
 
 // Sum of part[0..n) by a 256-thread workgroup in a fixed order (strided per-thread sums, xor
@@ -492,30 +497,11 @@ int ode_launch_norm(const double* part, int n, double count, double* out, hipStr
 extern "C" int gp_ode_rhs(const gp_head_weights* w, const float* pobj, float t32, float sigma, double coef,
                           const double* y, const double* const* kin, const double* acoef, int nk, double h, int rows,
                           int k, double* kout, void* workspace, size_t workspace_bytes, hipStream_t stream) {
-    GP_REQUIRE(w && pobj && y && kout && workspace && rows >= 1 && k >= 1, "ode_rhs: bad arguments");
-    GP_REQUIRE(nk >= 0 && nk < ODE_NK && (nk == 0 || (kin && acoef)), "ode_rhs: nk must be in [0, 6]");
-    GP_REQUIRE(workspace_bytes >= gp_ode_workspace_size(rows), "ode_rhs: workspace too small");
-    OdeStageArgs a = {};
-    a.w = *w;
-    a.pobj = pobj;
-    a.tproj = static_cast<const float*>(workspace);
-    a.sigma = sigma;
-    a.coef = coef;
-    a.y = y;
-    for (int j = 0; j < nk; ++j) {
-        GP_REQUIRE(kin[j] != nullptr, "ode_rhs: null stage pointer");
-        a.k[j] = kin[j];
-        a.a[j] = acoef[j];
-    }
-    a.nk = nk;
-    a.h = h;
-    a.kout = kout;
-    a.rows = rows;
-    a.kper = k;
-    int rc = ode_launch_times(w, &t32, 1, workspace, stream);
-    if (rc) return rc;
-    ode_launch_stage<0>(a, ode_nt(w, rows), stream);
-    return gp_check_launch("ode_stage_kernel");
+    return ode_rhs_once("ode_rhs", w, pobj, t32, sigma, coef, y, kin, acoef, nk, h, rows, k, kout, workspace,
+                        workspace_bytes, stream,
+                        [&](const OdeStageArgs& a) {
+                            return ode_launch_stage(a, ode_nt(w, rows), false, "ode_stage_kernel", stream);
+                        });
 }
 
 extern "C" int gp_ode_attempt(const gp_head_weights* w, const float* pobj, const float* t32_6, const float* sigma_6,
@@ -523,50 +509,12 @@ extern "C" int gp_ode_attempt(const gp_head_weights* w, const float* pobj, const
                               const double* b, const double* e, double h, double rtol, double atol, int rows, int k,
                               double* ynew, double* err_out, void* workspace, size_t workspace_bytes,
                               hipStream_t stream) {
-    GP_REQUIRE(w && pobj && t32_6 && sigma_6 && coef_6 && y && kslots && tableau_a && b && e && ynew && err_out &&
-                   workspace && rows >= 1 && k >= 1,
-               "ode_attempt: bad arguments");
-    GP_REQUIRE(workspace_bytes >= gp_ode_workspace_size(rows), "ode_attempt: workspace too small");
-    for (int j = 0; j < ODE_NK; ++j) GP_REQUIRE(kslots[j] != nullptr, "ode_attempt: null K slot");
-    const int nwg = ode_nwg(w, rows), nt = ode_nt(w, rows);
-    const float* tproj = static_cast<const float*>(workspace);
-    double* part = reinterpret_cast<double*>(static_cast<char*>(workspace) + ode_part_offset());
-    int rc = ode_launch_times(w, t32_6, 6, workspace, stream);
-    if (rc) return rc;
-    OdeStageArgs a = {};
-    a.w = *w;
-    a.pobj = pobj;
-    a.y = y;
-    a.h = h;
-    a.rows = rows;
-    a.kper = k;
-    a.rtol = rtol;
-    a.atol = atol;
-    for (int j = 0; j < ODE_NK; ++j) a.k[j] = kslots[j];
-    // stages 1..5: K_s = f(t + c_s h, y + (sum_{j<s} A[s][j] K_j) h)   (tableau_a: 6x6 row-major)
-    for (int s = 1; s < 6; ++s) {
-        a.tproj = tproj + (size_t)(s - 1) * 768;
-        a.sigma = sigma_6[s - 1];
-        a.coef = coef_6[s - 1];
-        a.nk = s;
-        for (int j = 0; j < s; ++j) a.a[j] = tableau_a[s * 6 + j];
-        a.kout = kslots[s];
-        ode_launch_stage<0>(a, nt, stream);
-    }
-    // y_new = y + (sum_{j<6} B_j K_j) h ; K_6 = f(t + h, y_new) ; error partials
-    a.tproj = tproj + (size_t)5 * 768;
-    a.sigma = sigma_6[5];
-    a.coef = coef_6[5];
-    a.nk = 6;
-    for (int j = 0; j < 6; ++j) a.a[j] = b[j];
-    for (int j = 0; j < ODE_NK; ++j) a.e[j] = e[j];
-    a.kout = kslots[6];
-    a.ynew = ynew;
-    a.part = part;
-    ode_launch_stage<1>(a, nt, stream);
-    hipLaunchKernelGGL(ode_norm_kernel, dim3(1), dim3(256), 0, stream, (const double*)part, nwg,
-                       (double)rows * 9.0, err_out);
-    return gp_check_launch("ode_stage_kernel<final>");
+    return ode_attempt_host(
+        "ode_attempt", w, pobj, t32_6, sigma_6, coef_6, y, kslots, tableau_a, b, e, h, rtol, atol, rows, k, ynew, err_out,
+        workspace, workspace_bytes, stream, [&] { return ode_nwg(w, rows); }, (double)rows * 9.0,
+        [&](const OdeStageArgs& a, bool last) {
+            return ode_launch_stage(a, ode_nt(w, rows), last, last ? "ode_stage_kernel<final>" : nullptr, stream);
+        });
 }
 
 // ------------------------------------------------------------------------------ likelihood (host-controlled)
@@ -577,30 +525,11 @@ extern "C" int gp_like_rhs(const gp_head_weights* w, const float* pobj, float t3
                            const double* y, const float* eps, const double* const* kin, const double* acoef, int nk,
                            double h, int rows, int k, double* kout, void* workspace, size_t workspace_bytes,
                            hipStream_t stream) {
-    GP_REQUIRE(w && pobj && y && eps && kout && workspace && rows >= 1 && k >= 1, "like_rhs: bad arguments");
-    GP_REQUIRE(nk >= 0 && nk < ODE_NK && (nk == 0 || (kin && acoef)), "like_rhs: nk must be in [0, 6]");
-    GP_REQUIRE(workspace_bytes >= gp_like_workspace_size(rows), "like_rhs: workspace too small");
-    OdeStageArgs a = {};
-    a.w = *w;
-    a.pobj = pobj;
-    a.tproj = static_cast<const float*>(workspace);
-    a.sigma = sigma;
-    a.coef = coef;
-    a.y = y;
-    for (int j = 0; j < nk; ++j) {
-        GP_REQUIRE(kin[j] != nullptr, "like_rhs: null stage pointer");
-        a.k[j] = kin[j];
-        a.a[j] = acoef[j];
-    }
-    a.nk = nk;
-    a.h = h;
-    a.kout = kout;
-    a.rows = rows;
-    a.kper = k;
-    int rc = ode_launch_times(w, &t32, 1, workspace, stream);
-    if (rc) return rc;
-    like_launch_stage<0>(a, eps, like_np(w, rows), stream);
-    return gp_check_launch("like_stage_kernel");
+    GP_REQUIRE(eps, "like_rhs: bad arguments");
+    return ode_rhs_once("like_rhs", w, pobj, t32, sigma, coef, y, kin, acoef, nk, h, rows, k, kout, workspace,
+                        workspace_bytes, stream, [&](const OdeStageArgs& a) {
+                            return like_launch_stage(a, eps, like_np(w, rows), false, "like_stage_kernel", stream);
+                        });
 }
 
 extern "C" int gp_like_attempt(const gp_head_weights* w, const float* pobj, const float* t32_6, const float* sigma_6,
@@ -608,49 +537,14 @@ extern "C" int gp_like_attempt(const gp_head_weights* w, const float* pobj, cons
                                const double* tableau_a, const double* b, const double* e, double h, double rtol,
                                double atol, int rows, int k, double* ynew, double* err_out, void* workspace,
                                size_t workspace_bytes, hipStream_t stream) {
-    GP_REQUIRE(w && pobj && t32_6 && sigma_6 && coef_6 && y && eps && kslots && tableau_a && b && e && ynew &&
-                   err_out && workspace && rows >= 1 && k >= 1,
-               "like_attempt: bad arguments");
-    GP_REQUIRE(workspace_bytes >= gp_like_workspace_size(rows), "like_attempt: workspace too small");
-    for (int j = 0; j < ODE_NK; ++j) GP_REQUIRE(kslots[j] != nullptr, "like_attempt: null K slot");
-    const int np = like_np(w, rows);
-    const int nwg = (rows + 16 * np - 1) / (16 * np);
-    const float* tproj = static_cast<const float*>(workspace);
-    double* part = reinterpret_cast<double*>(static_cast<char*>(workspace) + ode_part_offset());
-    int rc = ode_launch_times(w, t32_6, 6, workspace, stream);
-    if (rc) return rc;
-    OdeStageArgs a = {};
-    a.w = *w;
-    a.pobj = pobj;
-    a.y = y;
-    a.h = h;
-    a.rows = rows;
-    a.kper = k;
-    a.rtol = rtol;
-    a.atol = atol;
-    for (int j = 0; j < ODE_NK; ++j) a.k[j] = kslots[j];
-    for (int s = 1; s < 6; ++s) {
-        a.tproj = tproj + (size_t)(s - 1) * 768;
-        a.sigma = sigma_6[s - 1];
-        a.coef = coef_6[s - 1];
-        a.nk = s;
-        for (int j = 0; j < s; ++j) a.a[j] = tableau_a[s * 6 + j];
-        a.kout = kslots[s];
-        like_launch_stage<0>(a, eps, np, stream);
-    }
-    a.tproj = tproj + (size_t)5 * 768;
-    a.sigma = sigma_6[5];
-    a.coef = coef_6[5];
-    a.nk = 6;
-    for (int j = 0; j < 6; ++j) a.a[j] = b[j];
-    for (int j = 0; j < ODE_NK; ++j) a.e[j] = e[j];
-    a.kout = kslots[6];
-    a.ynew = ynew;
-    a.part = part;
-    like_launch_stage<1>(a, eps, np, stream);
-    hipLaunchKernelGGL(ode_norm_kernel, dim3(1), dim3(256), 0, stream, (const double*)part, nwg,
-                       (double)rows * 10.0, err_out);
-    return gp_check_launch("like_stage_kernel<final>");
+    GP_REQUIRE(eps, "like_attempt: bad arguments");
+    return ode_attempt_host(
+        "like_attempt", w, pobj, t32_6, sigma_6, coef_6, y, kslots, tableau_a, b, e, h, rtol, atol, rows, k, ynew,
+        err_out, workspace, workspace_bytes, stream,
+        [&] { return (rows + 16 * like_np(w, rows) - 1) / (16 * like_np(w, rows)); }, (double)rows * 10.0,
+        [&](const OdeStageArgs& a, bool last) {
+            return like_launch_stage(a, eps, like_np(w, rows), last, last ? "like_stage_kernel<final>" : nullptr, stream);
+        });
 }
 
 extern "C" int gp_ode_init_norms(const double* y0, const double* f0, const double* f1, long long n, double atol,
@@ -685,28 +579,35 @@ extern "C" int gp_ode_dense(const double* const* kslots, const double* P7x4, con
     return gp_check_launch("ode_dense_kernel");
 }
 
+int ode_denoise_begin(const char* who, const gp_head_weights* w, const float* pobj, float t32, float sigma, float g2,
+                      float step, const double* x, int rows, int k, const float* pts_center, double* pose, double* q,
+                      void* workspace, size_t workspace_bytes, hipStream_t stream, OdeDenoiseArgs* a) {
+    GP_REQUIRE(w && pobj && x && pts_center && pose && q && workspace && rows >= 1 && k >= 1, "%s: bad arguments", who);
+    GP_REQUIRE(workspace_bytes >= gp_ode_workspace_size(rows), "%s: workspace too small", who);
+    GP_TRY(ode_launch_times(w, &t32, 1, workspace, stream));
+    *a = OdeDenoiseArgs{};
+    a->w = *w;
+    a->pobj = pobj;
+    a->tproj = static_cast<const float*>(workspace);
+    a->sigma = sigma;
+    a->g2 = g2;
+    a->step = step;
+    a->x = x;
+    a->center = pts_center;
+    a->pose = pose;
+    a->q = q;
+    a->rows = rows;
+    a->kper = k;
+    return GP_OK;
+}
+
 // nt_rows: the row count that picks the tile class (rows; the whole batch's rows for a per-object slice)
-static int ode_denoise_impl(const gp_head_weights* w, const float* pobj, float t32, float sigma, float g2, float step,
-                            const double* x, int rows, int k, int nt_rows, const float* pts_center, double* pose,
-                            double* q, void* workspace, size_t workspace_bytes, hipStream_t stream) {
-    GP_REQUIRE(w && pobj && x && pts_center && pose && q && workspace && rows >= 1 && k >= 1,
-               "ode_denoise: bad arguments");
-    GP_REQUIRE(workspace_bytes >= gp_ode_workspace_size(rows), "ode_denoise: workspace too small");
-    int rc = ode_launch_times(w, &t32, 1, workspace, stream);
-    if (rc) return rc;
-    OdeDenoiseArgs a = {};
-    a.w = *w;
-    a.pobj = pobj;
-    a.tproj = static_cast<const float*>(workspace);
-    a.sigma = sigma;
-    a.g2 = g2;
-    a.step = step;
-    a.x = x;
-    a.center = pts_center;
-    a.pose = pose;
-    a.q = q;
-    a.rows = rows;
-    a.kper = k;
+static int ode_denoise_impl(const gp_head_weights* w, const float* pobj, const OdeDenoiseScalars& sc, const double* x,
+                            int rows, int k, int nt_rows, const float* pts_center, double* pose, double* q,
+                            void* workspace, size_t workspace_bytes, hipStream_t stream) {
+    OdeDenoiseArgs a;
+    GP_TRY(ode_denoise_begin("ode_denoise", w, pobj, sc.te, sc.sig, sc.g2, sc.step, x, rows, k, pts_center, pose, q,
+                             workspace, workspace_bytes, stream, &a));
     // the stage kernels' trunk and tile (exact fp32 without the f16 planes)
     const int nt = ode_nt(w, nt_rows);
     const dim3 grid((rows + 16 * nt - 1) / (16 * nt)), blk(EVAL_WV * 64);
@@ -719,7 +620,7 @@ static int ode_denoise_impl(const gp_head_weights* w, const float* pobj, float t
 extern "C" int gp_ode_denoise(const gp_head_weights* w, const float* pobj, float t32, float sigma, float g2,
                               float step, const double* x, int rows, int k, const float* pts_center, double* pose,
                               double* q, void* workspace, size_t workspace_bytes, hipStream_t stream) {
-    return ode_denoise_impl(w, pobj, t32, sigma, g2, step, x, rows, k, rows, pts_center, pose, q, workspace,
+    return ode_denoise_impl(w, pobj, {t32, sigma, g2, step}, x, rows, k, rows, pts_center, pose, q, workspace,
                             workspace_bytes, stream);
 }
 
@@ -853,85 +754,86 @@ struct OdeGlobal {
 
 static size_t ode_auto_ws_bytes(int part_n) { return auto_part_off() + sizeof(double) * (size_t)part_n + 256; }
 
-static int ode_auto_attempt_impl(const gp_head_weights* w, const float* pobj, int n, int what, double t_bound,
-                                 double direction, double rtol, double atol, double sig_min, double base,
-                                 double diff_scale, double* y0, double* y1, double* const* kslots,
-                                 const double* tableau_a, const double* b, const double* e, int rows, int k,
-                                 const OdeGlobal* g, void* workspace, size_t workspace_bytes, int* hstat,
-                                 hipStream_t stream, const gp_head_grad_weights* gw = nullptr) {
-    GP_REQUIRE(w && pobj && y0 && y1 && kslots && tableau_a && b && e && workspace && rows >= 1 && k >= 1 && n >= 0,
+// What every gp_ode_auto_attempt* entry hands on as it got it, in the entries' order
+struct OdeAutoParams {
+    const gp_head_weights* w;
+    const float* pobj;
+    int n, what;
+    double t_bound, direction, rtol, atol, sig_min, base, diff_scale;
+    double *y0, *y1;
+    double* const* kslots;
+    const double *tableau_a, *b, *e;
+    int rows, k;
+    void* workspace;
+    size_t workspace_bytes;
+    hipStream_t stream;
+};
+
+// g: a global-batch shard, or null; hstat: the host-mapped status words, or null; gw: the energy agent's
+// transposed weights, or null for the score agent
+static int ode_auto_attempt_impl(const OdeAutoParams& p, const OdeGlobal* g, int* hstat,
+                                 const gp_head_grad_weights* gw) {
+    GP_REQUIRE(p.w && p.pobj && p.y0 && p.y1 && p.kslots && p.tableau_a && p.b && p.e && p.workspace && p.rows >= 1 &&
+                   p.k >= 1 && p.n >= 0,
                "ode_auto_attempt: bad arguments");
-    for (int j = 0; j < ODE_NK; ++j) GP_REQUIRE(kslots[j] != nullptr, "ode_auto_attempt: null K slot");
-    char* ws = static_cast<char*>(workspace);
+    for (int j = 0; j < ODE_NK; ++j) GP_REQUIRE(p.kslots[j] != nullptr, "ode_auto_attempt: null K slot");
+    const int n = p.n, rows = p.rows;
+    const hipStream_t stream = p.stream;
+    char* ws = static_cast<char*>(p.workspace);
     OdeCtl* ctl = reinterpret_cast<OdeCtl*>(ws);
     float* tproj6 = reinterpret_cast<float*>(ws + auto_tproj_off());
     double* part = reinterpret_cast<double*>(ws + auto_part_off());
     // gw: the energy agent's stages (gp_ode_energy.hip), 16-row tiles whatever the trunk arithmetic of w
-    const int nt = gw ? 1 : ode_nt(w, g ? g->rows_total : rows);
+    const int nt = gw ? 1 : ode_nt(p.w, g ? g->rows_total : rows);
     const int nwg = (rows + 16 * nt - 1) / (16 * nt);   // this call's workgroups
     const int part_n = g ? g->part_n : nwg;
     GP_REQUIRE(!g || (g->part_off >= 0 && g->part_off + nwg <= part_n),
                "ode_auto_attempt: shard partials [%d, %d) outside %d", g ? g->part_off : 0, g ? g->part_off + nwg : 0,
                part_n);
-    GP_REQUIRE(workspace_bytes >= ode_auto_ws_bytes(part_n), "ode_auto_attempt: workspace too small");
-    OdeConsts kc = {t_bound, direction, rtol, atol, sig_min, base, diff_scale,
+    GP_REQUIRE(p.workspace_bytes >= ode_auto_ws_bytes(part_n), "ode_auto_attempt: workspace too small");
+    OdeConsts kc = {p.t_bound, p.direction, p.rtol, p.atol, p.sig_min, p.base, p.diff_scale,
                     (double)(g ? g->rows_total : rows) * 9.0, part_n};
     OdeCtl* cin = ctl + (n & 1);
     OdeCtl* cout = ctl + ((n + 1) & 1);
-    GP_REQUIRE(what >= 1 && what <= 3, "ode_auto_attempt: what must be 1 (control), 2 (stages) or 3 (both)");
-    if (what & 1) {
-        hipLaunchKernelGGL(ode_control_kernel, dim3(6, ODE_CTL_CHUNKS), dim3(HT), 0, stream, *w, (const OdeCtl*)cin,
+    GP_REQUIRE(p.what >= 1 && p.what <= 3, "ode_auto_attempt: what must be 1 (control), 2 (stages) or 3 (both)");
+    if (p.what & 1) {
+        hipLaunchKernelGGL(ode_control_kernel, dim3(6, ODE_CTL_CHUNKS), dim3(HT), 0, stream, *p.w, (const OdeCtl*)cin,
                            cout, (const double*)part, n > 0 ? 1 : 0, kc, tproj6, hstat, n);
         const int rc = gp_check_launch("ode_control_kernel");
-        if (rc || !(what & 2)) return rc;
+        if (rc || !(p.what & 2)) return rc;
     }
     OdeStageArgs a = {};
-    a.w = *w;
-    a.pobj = pobj;
+    a.w = *p.w;
+    a.pobj = p.pobj;
     a.rows = rows;
-    a.kper = k;
+    a.kper = p.k;
     a.part_off = g ? g->part_off : 0;
-    a.rtol = rtol;
-    a.atol = atol;
+    a.rtol = p.rtol;
+    a.atol = p.atol;
     a.ctl = cout;
     a.tproj6 = tproj6;
-    a.ybuf[0] = y0;
-    a.ybuf[1] = y1;
-    for (int j = 0; j < ODE_NK; ++j) a.kbuf[j] = kslots[j];
+    a.ybuf[0] = p.y0;
+    a.ybuf[1] = p.y1;
+    for (int j = 0; j < ODE_NK; ++j) a.kbuf[j] = p.kslots[j];
+    int rc;
     if (ode_fused()) {   // one launch per attempt (ode_attempt_kernel)
-        const OdeTableau tb = ode_tableau(tableau_a, b);
-        for (int j = 0; j < ODE_NK; ++j) a.e[j] = e[j];
+        const OdeTableau tb = ode_tableau(p.tableau_a, p.b);
+        for (int j = 0; j < ODE_NK; ++j) a.e[j] = p.e[j];
         a.part = part;
         if (gw) return ode_energy_launch_attempt(a, *gw, tb, stream);
         const dim3 grid(nwg), blk(EVAL_WV * 64);
-        head_dispatch(w->pe2_h ? X3P : 0, nt, [&](auto pl, auto ntc) {
+        head_dispatch(p.w->pe2_h ? X3P : 0, nt, [&](auto pl, auto ntc) {
             hipLaunchKernelGGL((ode_attempt_kernel<pl.value, ntc.value>), grid, blk, 0, stream, a, tb);
         });
-        const int rc = gp_check_launch("ode_attempt_kernel");
-        if (rc || !g) return rc;
-        GP_REQUIRE(g->exchange(g->ctx, n, part, part_n, stream) == 0, "ode_auto_attempt: partials exchange of attempt %d",
-                   n);
-        return GP_OK;
+        rc = gp_check_launch("ode_attempt_kernel");
+    } else {   // the six stage launches, their scalars from the controller's record
+        rc = ode_run_stages(
+            a, p.tableau_a, p.b, p.e, nullptr, part, [](OdeStageArgs& s, int st) { s.stage = st; },
+            [&](const OdeStageArgs& s, bool last) {
+                return gw ? ode_energy_launch_stage(s, *gw, last, stream)
+                          : ode_launch_stage(s, nt, last, last ? "ode_stage_kernel<auto>" : nullptr, stream);
+            });
     }
-    for (int s = 1; s < 6; ++s) {
-        a.stage = s;
-        a.nk = s;
-        for (int j = 0; j < s; ++j) a.a[j] = tableau_a[s * 6 + j];
-        if (gw) {
-            const int rc = ode_energy_launch_stage(a, *gw, false, stream);
-            if (rc) return rc;
-        } else {
-            ode_launch_stage<0>(a, nt, stream);
-        }
-    }
-    a.stage = 6;
-    a.nk = 6;
-    for (int j = 0; j < 6; ++j) a.a[j] = b[j];
-    for (int j = 0; j < ODE_NK; ++j) a.e[j] = e[j];
-    a.part = part;
-    if (gw) return ode_energy_launch_stage(a, *gw, true, stream);
-    ode_launch_stage<1>(a, nt, stream);
-    const int rc = gp_check_launch("ode_stage_kernel<auto>");
     if (rc || !g) return rc;
     GP_REQUIRE(g->exchange(g->ctx, n, part, part_n, stream) == 0, "ode_auto_attempt: partials exchange of attempt %d", n);
     return GP_OK;
@@ -943,8 +845,9 @@ extern "C" int gp_ode_auto_attempt(const gp_head_weights* w, const float* pobj, 
                                    double* const* kslots, const double* tableau_a, const double* b,
                                    const double* e, int rows, int k, void* workspace, size_t workspace_bytes,
                                    hipStream_t stream) {
-    return ode_auto_attempt_impl(w, pobj, n, what, t_bound, direction, rtol, atol, sig_min, base, diff_scale, y0, y1,
-                                 kslots, tableau_a, b, e, rows, k, nullptr, workspace, workspace_bytes, nullptr, stream);
+    return ode_auto_attempt_impl({w, pobj, n, what, t_bound, direction, rtol, atol, sig_min, base, diff_scale, y0, y1,
+                                  kslots, tableau_a, b, e, rows, k, workspace, workspace_bytes, stream},
+                                 nullptr, nullptr, nullptr);
 }
 
 extern "C" int gp_ode_auto_attempt_hs(const gp_head_weights* w, const float* pobj, int n, int what,
@@ -954,9 +857,9 @@ extern "C" int gp_ode_auto_attempt_hs(const gp_head_weights* w, const float* pob
                                       const double* e, int rows, int k, void* workspace, size_t workspace_bytes,
                                       int* host_status, hipStream_t stream) {
     GP_REQUIRE(host_status != nullptr, "ode_auto_attempt_hs: null status words");
-    return ode_auto_attempt_impl(w, pobj, n, what, t_bound, direction, rtol, atol, sig_min, base, diff_scale, y0, y1,
-                                 kslots, tableau_a, b, e, rows, k, nullptr, workspace, workspace_bytes, host_status,
-                                 stream);
+    return ode_auto_attempt_impl({w, pobj, n, what, t_bound, direction, rtol, atol, sig_min, base, diff_scale, y0, y1,
+                                  kslots, tableau_a, b, e, rows, k, workspace, workspace_bytes, stream},
+                                 nullptr, host_status, nullptr);
 }
 
 extern "C" int gp_ode_auto_attempt_energy(const gp_head_weights* w, const gp_head_grad_weights* gw, const float* pobj,
@@ -966,9 +869,9 @@ extern "C" int gp_ode_auto_attempt_energy(const gp_head_weights* w, const gp_hea
                                           const double* b, const double* e, int rows, int k, void* workspace,
                                           size_t workspace_bytes, int* host_status, hipStream_t stream) {
     GP_REQUIRE(ode_energy_weights_ok(gw), "ode_auto_attempt_energy: null transposed weights");
-    return ode_auto_attempt_impl(w, pobj, n, what, t_bound, direction, rtol, atol, sig_min, base, diff_scale, y0, y1,
-                                 kslots, tableau_a, b, e, rows, k, nullptr, workspace, workspace_bytes, host_status,
-                                 stream, gw);
+    return ode_auto_attempt_impl({w, pobj, n, what, t_bound, direction, rtol, atol, sig_min, base, diff_scale, y0, y1,
+                                  kslots, tableau_a, b, e, rows, k, workspace, workspace_bytes, stream},
+                                 nullptr, host_status, gw);
 }
 
 extern "C" int gp_ode_global_partials(int rows_total, int shard_rows_max, int shards, int split) {
@@ -997,8 +900,9 @@ extern "C" int gp_ode_auto_attempt_global(const gp_head_weights* w, const float*
     const int tile = 16 * ode_nt(w, rows_total);
     const int per = (shard_rows_max + tile - 1) / tile;
     OdeGlobal g = {rows_total, shards * per, shard * per, exchange, ctx};
-    return ode_auto_attempt_impl(w, pobj, n, what, t_bound, direction, rtol, atol, sig_min, base, diff_scale, y0, y1,
-                                 kslots, tableau_a, b, e, rows, k, &g, workspace, workspace_bytes, host_status, stream);
+    return ode_auto_attempt_impl({w, pobj, n, what, t_bound, direction, rtol, atol, sig_min, base, diff_scale, y0, y1,
+                                  kslots, tableau_a, b, e, rows, k, workspace, workspace_bytes, stream},
+                                 &g, host_status, nullptr);
 }
 
 // ============================================================================ whole sampler (C hosts)
@@ -1010,16 +914,14 @@ extern "C" int gp_ode_auto_attempt_global(const gp_head_weights* w, const float*
 // agent.py (PoseNet._ode) are the Python form of the same sequence.
 namespace {
 struct OdeSampleLayout {
-    size_t y[2], k[ODE_NK], f1, dense, scal, rhs_ws, auto_ws, total;
+    OdeStateBlock st;   // y and ynew: the two state buffers of the device controller
+    size_t dense, scal, rhs_ws, auto_ws, total;
 };
 OdeSampleLayout ode_sample_layout(int rows) {
     OdeSampleLayout L = {};
-    const size_t vec = align256((size_t)rows * 9 * sizeof(double));
     size_t off = 0;
-    for (int i = 0; i < 2; ++i) { L.y[i] = off; off += vec; }
-    for (int j = 0; j < ODE_NK; ++j) { L.k[j] = off; off += vec; }
-    L.f1 = off; off += vec;
-    L.dense = off; off += vec;
+    L.st = ode_state_layout(off, rows, 9);
+    L.dense = off; off += align256((size_t)rows * 9 * sizeof(double));
     L.scal = off; off += 256;
     L.rhs_ws = off; off += align256(gp_ode_workspace_size(rows));
     L.auto_ws = off; off += align256(gp_ode_auto_workspace_size(rows));
@@ -1095,10 +997,10 @@ static int ode_sample_impl(const gp_head_weights* w, const gp_head_grad_weights*
     StatusLease status;
     GP_REQUIRE(status.acquire(stream) == 0, "ode_sample: pinned status word / event");
     char* ws = static_cast<char*>(workspace);
-    double* y[2] = {reinterpret_cast<double*>(ws + L.y[0]), reinterpret_cast<double*>(ws + L.y[1])};
+    double* y[2] = {reinterpret_cast<double*>(ws + L.st.y), reinterpret_cast<double*>(ws + L.st.ynew)};
     double* K[ODE_NK];
-    for (int j = 0; j < ODE_NK; ++j) K[j] = reinterpret_cast<double*>(ws + L.k[j]);
-    double* f1 = reinterpret_cast<double*>(ws + L.f1);
+    for (int j = 0; j < ODE_NK; ++j) K[j] = reinterpret_cast<double*>(ws + L.st.k[j]);
+    double* f1 = reinterpret_cast<double*>(ws + L.st.f1);
     double* dense = reinterpret_cast<double*>(ws + L.dense);
     double* scal = reinterpret_cast<double*>(ws + L.scal);
     void* rws = ws + L.rhs_ws;
@@ -1125,8 +1027,7 @@ static int ode_sample_impl(const gp_head_weights* w, const gp_head_grad_weights*
     }
     if ((rc = gp_ode_init_norms(y[0], K[0], nullptr, n, atol, rtol, scal, stream))) return rc;
     double hs[3];
-    GP_REQUIRE(hipMemcpyAsync(hs, scal, 2 * sizeof(double), hipMemcpyDeviceToHost, stream) == hipSuccess &&
-                   hipStreamSynchronize(stream) == hipSuccess, "ode_sample: norm read");
+    GP_TRY(ode_copy_sync(hs, scal, 2 * sizeof(double), hipMemcpyDeviceToHost, stream, "ode_sample", "norm read"));
     const double interval = fabs(tf - t0);
     const double h0 = ode_init_h0(hs[0], hs[1], interval);
     {   // f(t0 + h0 dir, y0 + h0 dir f0)
@@ -1136,8 +1037,7 @@ static int ode_sample_impl(const gp_head_weights* w, const gp_head_grad_weights*
         if ((rc = rhs((float)t, ode_coef(t, dscale), kin, &a1, 1, h0 * dir, f1))) return rc;
     }
     if ((rc = gp_ode_init_norms(y[0], K[0], f1, n, atol, rtol, scal, stream))) return rc;
-    GP_REQUIRE(hipMemcpyAsync(hs + 2, scal + 2, sizeof(double), hipMemcpyDeviceToHost, stream) == hipSuccess &&
-                   hipStreamSynchronize(stream) == hipSuccess, "ode_sample: norm read");
+    GP_TRY(ode_copy_sync(hs + 2, scal + 2, sizeof(double), hipMemcpyDeviceToHost, stream, "ode_sample", "norm read"));
 
     // ---- device-controlled attempts, one enqueued ahead of the status read
     OdeCtl c0 = {};
@@ -1145,21 +1045,20 @@ static int ode_sample_impl(const gp_head_weights* w, const gp_head_grad_weights*
     c0.h_abs = ode_init_h_abs(h0, hs[1], hs[2], interval);
     c0.nfev = 2;
     for (int j = 0; j < ODE_NK; ++j) c0.kidx[j] = j;
-    GP_REQUIRE(hipMemcpyAsync(aws, &c0, sizeof(OdeCtl), hipMemcpyHostToDevice, stream) == hipSuccess &&
-                   hipStreamSynchronize(stream) == hipSuccess, "ode_sample: controller record");
+    GP_TRY(ode_copy_sync(aws, &c0, sizeof(OdeCtl), hipMemcpyHostToDevice, stream, "ode_sample", "controller record"));
     const char* ctl = static_cast<const char*>(aws);   // OdeCtl[2]; attempt n's control writes parity (n + 1) & 1
     int* hs_dev = status.map(false);
     auto launch = [&](int n, int what) {
-        return ode_auto_attempt_impl(w, pobj, n, what, tf, dir, rtol, atol, kSigMin, kBase, dscale, y[0], y[1], K,
-                                     kA6, kB6, kE7, rows, k, nullptr, aws, aws_b, hs_dev, stream, gw);
+        return ode_auto_attempt_impl({w, pobj, n, what, tf, dir, rtol, atol, kSigMin, kBase, dscale, y[0], y[1], K, kA6,
+                                      kB6, kE7, rows, k, aws, aws_b, stream},
+                                     nullptr, hs_dev, gw);
     };
     auto stat_src = [&](int n) { return ctl + ((n + 1) & 1) * sizeof(OdeCtl) + offsetof(OdeCtl, status); };
     int a = 0;
     if ((rc = ode_run_attempts(status, hs_dev, false, launch, stat_src, "ode_sample", &a))) return rc;
     OdeCtl c;
-    GP_REQUIRE(hipMemcpyAsync(&c, ctl + ((a + 2) & 1) * sizeof(OdeCtl), sizeof(OdeCtl), hipMemcpyDeviceToHost,
-                              stream) == hipSuccess &&
-                   hipStreamSynchronize(stream) == hipSuccess, "ode_sample: final record");
+    GP_TRY(ode_copy_sync(&c, ctl + ((a + 2) & 1) * sizeof(OdeCtl), sizeof(OdeCtl), hipMemcpyDeviceToHost, stream,
+                         "ode_sample", "final record"));
     status.pending = false;
     if (status_out) *status_out = c.status;
     if (nfev_out) *nfev_out = c.nfev;
@@ -1171,21 +1070,17 @@ static int ode_sample_impl(const gp_head_weights* w, const gp_head_grad_weights*
         const double* ks[ODE_NK];
         for (int j = 0; j < ODE_NK; ++j) ks[j] = K[c.kidx[j]];
         std::swap(ks[0], ks[ODE_NK - 1]);   // undo the FSAL swap of the accepted step
-        GP_REQUIRE(hipMemcpyAsync(scal + 7, &eps, sizeof(double), hipMemcpyHostToDevice, stream) == hipSuccess &&
-                       hipStreamSynchronize(stream) == hipSuccess, "ode_sample: t_eval");
+        GP_TRY(ode_copy_sync(scal + 7, &eps, sizeof(double), hipMemcpyHostToDevice, stream, "ode_sample", "t_eval"));
         if ((rc = gp_ode_dense(ks, kP74, y[c.yi ^ 1], scal + 7, 0, 1, 0, 0, c.t_old, c.t - c.t_old, n, dense, stream)))
             return rc;
         x = dense;
     }
-    // ---- denoise (samplers.py:240-249) with eps's scalars: a float32 1-element tensor for g
-    const float te = (float)eps;
-    const float sig = sigma32(te);
-    const float g = sig * (float)dscale;
-    const float step = (float)((1.0 - eps) / (steps > 0 ? steps : 1000));
+    // ---- denoise (samplers.py:240-249) with eps's scalars
+    const OdeDenoiseScalars ds = ode_denoise_scalars(eps, steps);
     if (gw)
-        return gp_ode_denoise_energy(w, gw, pobj, te, sig, g * g, step, x, rows, k, pts_center, pose, q, rws, rws_b,
-                                     stream);
-    return gp_ode_denoise(w, pobj, te, sig, g * g, step, x, rows, k, pts_center, pose, q, rws, rws_b, stream);
+        return gp_ode_denoise_energy(w, gw, pobj, ds.te, ds.sig, ds.g2, ds.step, x, rows, k, pts_center, pose, q, rws,
+                                     rws_b, stream);
+    return gp_ode_denoise(w, pobj, ds.te, ds.sig, ds.g2, ds.step, x, rows, k, pts_center, pose, q, rws, rws_b, stream);
 }
 
 extern "C" int gp_ode_sample(const gp_head_weights* w, const float* pobj, const float* x0, int rows, int k, double T0,
@@ -1312,23 +1207,8 @@ __global__ __launch_bounds__(EVAL_WV * 64) void ode_obj_attempt_kernel(OdeObjArg
     __shared__ const double* kin[ODE_NK];
     const int tid = threadIdx.x;
     const int r0 = blockIdx.x * ROWS;
-    int act = 0;
-    if (tid < ROWS) {
-        const int o = obj_of_row(r0 + tid, a.rows, a.kper);
-        const OdeObjRec* rc = a.rec + o;
-        act = (r0 + tid < a.rows) && rc->active != 0;
-        obj[tid] = o;
-        ract[tid] = act;
-        rpend[tid] = rc->pend;
-        rh[tid] = rc->h;
-    } else if (tid < ROWS + 36) {
-        tab[tid - ROWS] = a.single ? 1.0 : tb.A[tid - ROWS];
-    } else if (tid < ROWS + 42) {
-        tab[tid - ROWS] = tb.B[tid - ROWS - 36];
-    } else if (tid < ROWS + 42 + ODE_NK) {
-        kin[tid - ROWS - 42] = a.k[tid - ROWS - 42];
-    }
-    if (!__syncthreads_or(act)) return;   // none of this workgroup's objects runs
+    // none of this workgroup's objects runs: done
+    if (!ode_obj_rows_to_lds<ROWS, false>(a, tb, r0, obj, ract, rpend, rh, tab, kin)) return;
     if (a.single) {
         const SplitScalars hs = load_split_scalars<PL>(a.w);
         if (a.single == 1)
@@ -1599,17 +1479,15 @@ int ode_obj_solve(const OdeObjSolve& s, const std::function<int(const OdeObjRec*
     // one evaluation on host-built records: upload, their rows of slot 0, the stage, the norms and their read-back
     auto probe = [&](int parity, int single) -> int {
         OdeObjRec* r = rec + (size_t)parity * nobj;
-        GP_REQUIRE(hipMemcpyAsync(r, hrec.data(), sizeof(OdeObjRec) * (size_t)nobj, hipMemcpyHostToDevice, stream) ==
-                           hipSuccess && hipStreamSynchronize(stream) == hipSuccess, "%s: records", s.who);
+        GP_TRY(ode_copy_sync(r, hrec.data(), sizeof(OdeObjRec) * (size_t)nobj, hipMemcpyHostToDevice, stream, s.who,
+                             "records"));
         int prc;
         if ((prc = ode_obj_launch_control(s.w, s.pobj, r, nullptr, nullptr, 0, 0, 1, kc, s.k, nobj, s.init, s.count,
                                           nullptr, s.dstat, 0, stream)) ||
             (prc = stages(r, single)) || (prc = init_norms(single == 2)))
             return prc;
-        GP_REQUIRE(hipMemcpyAsync(hn.data(), s.norms, sizeof(double) * 3 * (size_t)nobj, hipMemcpyDeviceToHost,
-                                  stream) == hipSuccess && hipStreamSynchronize(stream) == hipSuccess,
-                   "%s: norm read", s.who);
-        return GP_OK;
+        return ode_copy_sync(hn.data(), s.norms, sizeof(double) * 3 * (size_t)nobj, hipMemcpyDeviceToHost, stream, s.who,
+                             "norm read");
     };
     {   // f(t0)
         OdeObjRec r = {};
@@ -1640,8 +1518,8 @@ int ode_obj_solve(const OdeObjSolve& s, const std::function<int(const OdeObjRec*
         r.nfev = 2;
         hrec[(size_t)b] = r;
     }
-    GP_REQUIRE(hipMemcpyAsync(rec, hrec.data(), sizeof(OdeObjRec) * (size_t)nobj, hipMemcpyHostToDevice, stream) ==
-                       hipSuccess && hipStreamSynchronize(stream) == hipSuccess, "%s: records", s.who);
+    GP_TRY(ode_copy_sync(rec, hrec.data(), sizeof(OdeObjRec) * (size_t)nobj, hipMemcpyHostToDevice, stream, s.who,
+                         "records"));
 
     // ---- the attempts, one enqueued ahead of the status read; the loop ends when no object runs
     int* hs_dev = status.map(true);
@@ -1656,8 +1534,8 @@ int ode_obj_solve(const OdeObjSolve& s, const std::function<int(const OdeObjRec*
     int at = 0;
     if ((rc = ode_run_attempts(status, hs_dev, true, launch, [&](int) { return s.dstat; }, s.who, &at))) return rc;
     *fin = rec + (size_t)((at + 2) & 1) * nobj;
-    GP_REQUIRE(hipMemcpyAsync(hrec.data(), *fin, sizeof(OdeObjRec) * (size_t)nobj, hipMemcpyDeviceToHost, stream) ==
-                       hipSuccess && hipStreamSynchronize(stream) == hipSuccess, "%s: final records", s.who);
+    GP_TRY(ode_copy_sync(hrec.data(), *fin, sizeof(OdeObjRec) * (size_t)nobj, hipMemcpyDeviceToHost, stream, s.who,
+                         "final records"));
     status.pending = false;
     bool bad = false;
     for (int b = 0; b < nobj; ++b) {
@@ -1671,18 +1549,15 @@ int ode_obj_solve(const OdeObjSolve& s, const std::function<int(const OdeObjRec*
 
 namespace {
 struct OdeObjLayout {
-    size_t y, ynew, k[ODE_NK], f1, xout, den_ws, total;
+    OdeStateBlock st;
+    size_t xout, den_ws, total;
     OdeObjTail tail;
 };
 OdeObjLayout ode_obj_layout(int rows, int nobj) {
     OdeObjLayout L = {};
-    const size_t vec = align256((size_t)rows * 9 * sizeof(double));
     size_t off = 0;
-    L.y = off; off += vec;
-    L.ynew = off; off += vec;
-    for (int j = 0; j < ODE_NK; ++j) { L.k[j] = off; off += vec; }
-    L.f1 = off; off += vec;
-    L.xout = off; off += vec;
+    L.st = ode_state_layout(off, rows, 9);
+    L.xout = off; off += align256((size_t)rows * 9 * sizeof(double));
     L.tail = ode_obj_tail_layout(off, rows, nobj);
     L.den_ws = off; off += align256(gp_ode_workspace_size(rows));
     L.total = off;
@@ -1718,23 +1593,10 @@ extern "C" int gp_ode_sample_object(const gp_head_weights* w, const float* pobj,
     const int nt = ode_nt(w, rows_total);   // the whole batch's tile class
     const int nwg = (rows + 16 * nt - 1) / (16 * nt);
 
-    OdeObjArgs a = {};
-    a.w = *w;
-    a.init = sv.init;
-    a.zrow = sv.zrow;
-    a.y = dptr(L.y);
-    a.ynew = dptr(L.ynew);
-    for (int j = 0; j < ODE_NK; ++j) {
-        a.k[j] = dptr(L.k[j]);
-        a.e[j] = kE7[j];
-    }
-    a.f1 = dptr(L.f1);
-    a.rowsq = sv.rowsq;
-    a.rtol = rtol;
-    a.atol = atol;
-    a.rows = rows;
-    a.kper = k;
-    a.nobj = nobj;
+    double* K[ODE_NK];
+    for (int j = 0; j < ODE_NK; ++j) K[j] = dptr(L.st.k[j]);
+    OdeObjArgs a = ode_obj_args<OdeObjArgs>(w, sv.init, sv.zrow, dptr(L.st.y), dptr(L.st.ynew), K, dptr(L.st.f1),
+                                            sv.rowsq, rtol, atol, rows, k);
     const OdeTableau tb = ode_tableau();
     auto stages = [&](const OdeObjRec* r, int single) {
         a.rec = r;
@@ -1775,12 +1637,8 @@ extern "C" int gp_ode_sample_object(const gp_head_weights* w, const float* pobj,
     fa.out = dptr(L.xout);
     hipLaunchKernelGGL(ode_obj_final_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, fa);
     if ((rc = gp_check_launch("ode_obj_final_kernel"))) return rc;
-    // ---- denoise (samplers.py:240-249) with eps's scalars: a float32 1-element tensor for g
-    const float te = (float)eps;
-    const float sig = sigma32(te);
-    const float g = sig * (float)diff_scale();
-    const float step = (float)((1.0 - eps) / (steps > 0 ? steps : 1000));
-    return ode_denoise_impl(w, pobj, te, sig, g * g, step, fa.out, rows, k, rows_total, pts_center, pose, q,
+    // ---- denoise (samplers.py:240-249) with eps's scalars
+    return ode_denoise_impl(w, pobj, ode_denoise_scalars(eps, steps), fa.out, rows, k, rows_total, pts_center, pose, q,
                             ws + L.den_ws, gp_ode_workspace_size(rows), stream);
 }
 

@@ -9,7 +9,9 @@
 // gp_energy_score_eval on float(y_in) bit for bit. The prologue (ode_stage_in), K = coef * (double)s, y_new, the
 // error terms (ode_err_term) and the workgroup partial (ode_block_partial) are gp_ode.h's, one definition each.
 // Tiles are 16 rows and 8 waves, exact fp32 whatever arithmetic the score kernels run (the reverse pass has no
-// f16x3 form). The control, norm, dense-output, time-row and init-norm kernels are gp_ode.hip's, unchanged.
+// f16x3 form). The control, norm, dense-output, time-row and init-norm kernels are gp_ode.hip's, unchanged, and
+// the entries at the end of this file are gp_ode.h's host sequences (ode_rhs_once, ode_attempt_host,
+// ode_denoise_begin) around this file's launches.
 //
 // A translation unit of its own: a sibling instantiation in gp_score.hip once moved the register assignment of
 // pc_step_kernel<1,8,0> (DESIGN "Energy model as a score model"); gp_ode.hip's kernels compile to the assembly
@@ -119,10 +121,7 @@ __global__ __launch_bounds__(EVAL_WV * 64) void ode_energy_attempt_kernel(OdeSta
     __shared__ const double* kin[ODE_NK];
     const OdeCtl* c = a.ctl;
     if (!c->active) return;
-    const int tid = threadIdx.x;
-    if (tid < 36) tab[tid] = tb.A[tid];
-    else if (tid < 42) tab[tid] = tb.B[tid - 36];
-    else if (tid < 42 + ODE_NK) kin[tid - 42] = a.kbuf[c->kidx[tid - 42]];
+    ode_attempt_to_lds(a, c, tb, tab, kin);
     const double* y = a.ybuf[c->yi];
     const double h = c->h;
     __syncthreads();
@@ -214,30 +213,10 @@ extern "C" int gp_ode_rhs_energy(const gp_head_weights* w, const gp_head_grad_we
                                  float t32, float sigma, double coef, const double* y, const double* const* kin,
                                  const double* acoef, int nk, double h, int rows, int k, double* kout,
                                  void* workspace, size_t workspace_bytes, hipStream_t stream) {
-    GP_REQUIRE(w && ode_energy_weights_ok(gw) && pobj && y && kout && workspace && rows >= 1 && k >= 1 && sigma > 0.f,
-               "ode_rhs_energy: bad arguments");
-    GP_REQUIRE(nk >= 0 && nk < ODE_NK && (nk == 0 || (kin && acoef)), "ode_rhs_energy: nk must be in [0, 6]");
-    GP_REQUIRE(workspace_bytes >= gp_ode_workspace_size(rows), "ode_rhs_energy: workspace too small");
-    OdeStageArgs a = {};
-    a.w = *w;
-    a.pobj = pobj;
-    a.tproj = static_cast<const float*>(workspace);
-    a.sigma = sigma;
-    a.coef = coef;
-    a.y = y;
-    for (int j = 0; j < nk; ++j) {
-        GP_REQUIRE(kin[j] != nullptr, "ode_rhs_energy: null stage pointer");
-        a.k[j] = kin[j];
-        a.a[j] = acoef[j];
-    }
-    a.nk = nk;
-    a.h = h;
-    a.kout = kout;
-    a.rows = rows;
-    a.kper = k;
-    const int rc = ode_launch_times(w, &t32, 1, workspace, stream);
-    if (rc) return rc;
-    return ode_energy_launch_stage(a, *gw, false, stream);
+    GP_REQUIRE(ode_energy_weights_ok(gw) && sigma > 0.f, "ode_rhs_energy: bad arguments");
+    return ode_rhs_once("ode_rhs_energy", w, pobj, t32, sigma, coef, y, kin, acoef, nk, h, rows, k, kout, workspace,
+                        workspace_bytes, stream,
+                        [&](const OdeStageArgs& a) { return ode_energy_launch_stage(a, *gw, false, stream); });
 }
 
 extern "C" int gp_ode_attempt_energy(const gp_head_weights* w, const gp_head_grad_weights* gw, const float* pobj,
@@ -246,74 +225,22 @@ extern "C" int gp_ode_attempt_energy(const gp_head_weights* w, const gp_head_gra
                                      const double* e, double h, double rtol, double atol, int rows, int k,
                                      double* ynew, double* err_out, void* workspace, size_t workspace_bytes,
                                      hipStream_t stream) {
-    GP_REQUIRE(w && ode_energy_weights_ok(gw) && pobj && t32_6 && sigma_6 && coef_6 && y && kslots && tableau_a && b &&
-                   e && ynew && err_out && workspace && rows >= 1 && k >= 1,
-               "ode_attempt_energy: bad arguments");
-    GP_REQUIRE(workspace_bytes >= gp_ode_workspace_size(rows), "ode_attempt_energy: workspace too small");
-    for (int j = 0; j < ODE_NK; ++j) GP_REQUIRE(kslots[j] != nullptr, "ode_attempt_energy: null K slot");
+    GP_REQUIRE(ode_energy_weights_ok(gw) && sigma_6, "ode_attempt_energy: bad arguments");
     for (int s = 0; s < 6; ++s) GP_REQUIRE(sigma_6[s] > 0.f, "ode_attempt_energy: sigma must be positive");
-    const int nwg = (rows + 15) / 16;
-    const float* tproj = static_cast<const float*>(workspace);
-    double* part = reinterpret_cast<double*>(static_cast<char*>(workspace) + ode_part_offset());
-    int rc = ode_launch_times(w, t32_6, 6, workspace, stream);
-    if (rc) return rc;
-    OdeStageArgs a = {};
-    a.w = *w;
-    a.pobj = pobj;
-    a.y = y;
-    a.h = h;
-    a.rows = rows;
-    a.kper = k;
-    a.rtol = rtol;
-    a.atol = atol;
-    for (int j = 0; j < ODE_NK; ++j) a.k[j] = kslots[j];
-    // stages 1..5: K_s = f(t + c_s h, y + (sum_{j<s} A[s][j] K_j) h)   (tableau_a: 6x6 row-major)
-    for (int s = 1; s < 6; ++s) {
-        a.tproj = tproj + (size_t)(s - 1) * 768;
-        a.sigma = sigma_6[s - 1];
-        a.coef = coef_6[s - 1];
-        a.nk = s;
-        for (int j = 0; j < s; ++j) a.a[j] = tableau_a[s * 6 + j];
-        a.kout = kslots[s];
-        if ((rc = ode_energy_launch_stage(a, *gw, false, stream))) return rc;
-    }
-    // y_new = y + (sum_{j<6} B_j K_j) h ; K_6 = f(t + h, y_new) ; error partials
-    a.tproj = tproj + (size_t)5 * 768;
-    a.sigma = sigma_6[5];
-    a.coef = coef_6[5];
-    a.nk = 6;
-    for (int j = 0; j < 6; ++j) a.a[j] = b[j];
-    for (int j = 0; j < ODE_NK; ++j) a.e[j] = e[j];
-    a.kout = kslots[6];
-    a.ynew = ynew;
-    a.part = part;
-    if ((rc = ode_energy_launch_stage(a, *gw, true, stream))) return rc;
-    return ode_launch_norm(part, nwg, (double)rows * 9.0, err_out, stream);
+    return ode_attempt_host(
+        "ode_attempt_energy", w, pobj, t32_6, sigma_6, coef_6, y, kslots, tableau_a, b, e, h, rtol, atol, rows, k, ynew,
+        err_out, workspace, workspace_bytes, stream, [&] { return (rows + 15) / 16; }, (double)rows * 9.0,
+        [&](const OdeStageArgs& a, bool last) { return ode_energy_launch_stage(a, *gw, last, stream); });
 }
 
 extern "C" int gp_ode_denoise_energy(const gp_head_weights* w, const gp_head_grad_weights* gw, const float* pobj,
                                      float t32, float sigma, float g2, float step, const double* x, int rows, int k,
                                      const float* pts_center, double* pose, double* q, void* workspace,
                                      size_t workspace_bytes, hipStream_t stream) {
-    GP_REQUIRE(w && ode_energy_weights_ok(gw) && pobj && x && pts_center && pose && q && workspace && rows >= 1 &&
-                   k >= 1 && sigma > 0.f,
-               "ode_denoise_energy: bad arguments");
-    GP_REQUIRE(workspace_bytes >= gp_ode_workspace_size(rows), "ode_denoise_energy: workspace too small");
-    const int rc = ode_launch_times(w, &t32, 1, workspace, stream);
-    if (rc) return rc;
-    OdeDenoiseArgs a = {};
-    a.w = *w;
-    a.pobj = pobj;
-    a.tproj = static_cast<const float*>(workspace);
-    a.sigma = sigma;
-    a.g2 = g2;
-    a.step = step;
-    a.x = x;
-    a.center = pts_center;
-    a.pose = pose;
-    a.q = q;
-    a.rows = rows;
-    a.kper = k;
+    GP_REQUIRE(ode_energy_weights_ok(gw) && sigma > 0.f, "ode_denoise_energy: bad arguments");
+    OdeDenoiseArgs a;
+    GP_TRY(ode_denoise_begin("ode_denoise_energy", w, pobj, t32, sigma, g2, step, x, rows, k, pts_center, pose, q,
+                             workspace, workspace_bytes, stream, &a));
     hipLaunchKernelGGL(ode_energy_denoise_kernel, dim3((rows + 15) / 16), dim3(EVAL_WV * 64), 0, stream, a, *gw);
     return gp_check_launch("ode_energy_denoise_kernel");
 }

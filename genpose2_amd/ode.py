@@ -14,7 +14,10 @@ Python/NumPy scalar types (scipy 1.15 ``_ivp/rk.py``: ``RK45``, ``rk_step``, ``_
 ``OdeSolver.step``; ``_ivp/ivp.py``: ``solve_ivp`` t_eval handling). The reference pins scipy only as
 ``scipy`` (requirements.txt:2, commented ``scipy==1.12.0``). The arithmetic lives in a backend:
 ``DeviceRk45`` (HIP, the product path) or ``NumpyRk45`` (scipy's own NumPy expressions; used by the
-CPU tests to hold the controller to ``solve_ivp`` exactly).
+CPU tests to hold the controller to ``solve_ivp`` exactly). The three device backends (score, energy, likelihood)
+share one ``_rhs`` and one ``attempt`` in ``DeviceRk45``; a backend's ``_entry`` names what differs (the library
+entry, its weight arguments, the extra pointer behind y, the stage scalars' source). ``_norms`` and ``_dense`` wrap
+the two launches that more than one caller makes.
 """
 from __future__ import annotations
 
@@ -23,7 +26,7 @@ import os
 import threading
 import time
 import warnings
-from typing import List, Optional, Tuple
+from typing import Callable, List, NamedTuple, Optional, Tuple
 
 import numpy as np
 import torch
@@ -285,13 +288,33 @@ def stage_scalars(ts: List[float]):
     return (np.ascontiguousarray(t32), np.ascontiguousarray(sig), np.ascontiguousarray(coef, dtype=np.float64))
 
 
+def _dense(lib, kslots, y_old: torch.Tensor, tev: torch.Tensor, i0: int, i1: int, base: int, rev: int, t_old, h,
+           out: torch.Tensor, stream) -> None:
+    """gp_ode_dense: the dense output of the step (t_old, h) with stages `kslots` from `y_old` at tev[i0:i1] into
+    the rows of `out` (row (i - base), or (base - i) with rev)."""
+    check(lib.gp_ode_dense(_ptr_array(kslots), _P74.ctypes.data_as(ctypes.c_void_p), ctypes.c_void_p(y_old.data_ptr()),
+                           ctypes.c_void_p(tev.data_ptr()), i0, i1, base, rev, float(t_old), float(h), y_old.numel(),
+                           ctypes.c_void_p(out.data_ptr()), stream), "ode_dense")
+
+
+class _Entry(NamedTuple):
+    """What a backend's "rhs" or "attempt" call is made of (DeviceRk45._entry)."""
+    fn: Callable          # the library entry
+    head: tuple           # its leading weight arguments
+    extra: tuple          # the extra pointers placed after y
+    scalars: Callable     # the source of an attempt's stage scalars
+    what: str             # the call's name in messages
+
+
 class DeviceRk45:
-    """State y, K_0..K_6 and y_new as fp64 (R*9) device tensors; every RHS is a HIP launch. ``energy_grad``: the
-    energy agent's backend -- the score of every right-hand side is the energy's gradient (gp_ode_rhs_energy,
-    gp_ode_attempt_energy; rk45_device then runs gp_ode_auto_attempt_energy), the rest is shared."""
+    """State y, K_0..K_6 and y_new as fp64 (R * entries) device tensors; every RHS is a HIP launch. ``entries``: state
+    entries per row (9 pose entries; 10 for the likelihood's pose and logp), which sizes every vector once.
+    ``energy_grad``: the energy agent's backend -- the score of every right-hand side is the energy's gradient
+    (gp_ode_rhs_energy, gp_ode_attempt_energy; rk45_device then runs gp_ode_auto_attempt_energy), the rest is shared.
+    What differs between the backends' right-hand sides and attempts is _entry's answer alone."""
 
     def __init__(self, heads, pobj: torch.Tensor, y0: torch.Tensor, k: int, rtol: float = 1e-5,
-                 atol: float = 1e-5, energy_grad: bool = False):
+                 atol: float = 1e-5, energy_grad: bool = False, entries: int = arch.POSE_DIM):
         self.lib = _lib.load()
         self.h = heads
         self.energy_grad = bool(energy_grad)
@@ -299,8 +322,8 @@ class DeviceRk45:
             self.err_pow = self._device_err_pow
         self.dev = heads.device
         self.pobj = pobj
-        self.R = y0.numel() // arch.POSE_DIM
-        self.n = self.R * arch.POSE_DIM
+        self.R = y0.numel() // entries
+        self.n = self.R * entries
         self.k = int(k)
         self.rtol, self.atol = float(rtol), float(atol)
         self.y = y0.reshape(-1).to(self.dev, torch.float64).contiguous()
@@ -321,11 +344,11 @@ class DeviceRk45:
         nk = len(kin)
         karr = _ptr_array(kin) if nk else None
         aarr = (ctypes.c_double * nk)(*acoef) if nk else None
-        fn, head = self._entry("gp_ode_rhs")
-        check(fn(*head, ctypes.c_void_p(self.pobj.data_ptr()), t32, sig, coef,
-                 ctypes.c_void_p(self.y.data_ptr()), karr, aarr, nk, float(h), self.R, self.k,
-                 ctypes.c_void_p(kout.data_ptr()), ctypes.c_void_p(self.ws.data_ptr()),
-                 self.ws.numel(), self._s()), "ode_rhs")
+        en = self._entry("rhs")
+        check(en.fn(*en.head, ctypes.c_void_p(self.pobj.data_ptr()), t32, sig, coef,
+                    ctypes.c_void_p(self.y.data_ptr()), *en.extra, karr, aarr, nk, float(h), self.R, self.k,
+                    ctypes.c_void_p(kout.data_ptr()), ctypes.c_void_p(self.ws.data_ptr()),
+                    self.ws.numel(), self._s()), en.what)
 
     def _device_stage_scalars(self, ts: List[float]):
         """stage_scalars with the powers taken on the device: the control kernel's expressions (gp_ode.hip
@@ -348,11 +371,21 @@ class DeviceRk45:
         e = torch.tensor([float(error_norm)], dtype=torch.float64, device=self.dev)
         return np.float64(torch.pow(e, torch.full_like(e, ERROR_EXPONENT)).cpu().numpy()[0])
 
-    def _entry(self, name: str):
-        """(library entry, its leading weight arguments): `name`, or its energy form with the transposed weights."""
+    def _entry(self, name: str) -> _Entry:
+        """The backend's "rhs" or "attempt" call: gp_ode_<name>, or its energy form with the transposed weights and
+        the device's powers."""
+        w = ctypes.byref(self.h.w)
         if self.energy_grad:
-            return getattr(self.lib, name + "_energy"), (ctypes.byref(self.h.w), ctypes.byref(self.h.grad_weights))
-        return getattr(self.lib, name), (ctypes.byref(self.h.w),)
+            return _Entry(getattr(self.lib, f"gp_ode_{name}_energy"), (w, ctypes.byref(self.h.grad_weights)), (),
+                          self._device_stage_scalars, "ode_" + name)
+        return _Entry(getattr(self.lib, "gp_ode_" + name), (w,), (), stage_scalars, "ode_" + name)
+
+    def _norms(self, y: torch.Tensor, f0: torch.Tensor, f1: Optional[torch.Tensor], n: int):
+        """gp_ode_init_norms over n entries: (d0, d1) of y and f0, or with f1 the norm of f1 - f0."""
+        check(self.lib.gp_ode_init_norms(ctypes.c_void_p(y.data_ptr()), ctypes.c_void_p(f0.data_ptr()),
+                                         None if f1 is None else ctypes.c_void_p(f1.data_ptr()), n, self.atol,
+                                         self.rtol, ctypes.c_void_p(self.scal.data_ptr()), self._s()), "ode_init_norms")
+        return self.scal[:2].cpu().numpy() if f1 is None else self.scal[2:3].cpu().numpy()[0]
 
     def set_t_eval(self, t_eval, direction, keep_all):
         self.t_eval = t_eval
@@ -367,34 +400,28 @@ class DeviceRk45:
         self._rhs(t, [], [], 0.0, self.K[0])
 
     def init_norms(self):
-        check(self.lib.gp_ode_init_norms(ctypes.c_void_p(self.y.data_ptr()), ctypes.c_void_p(self.K[0].data_ptr()),
-                                         None, self.n, self.atol, self.rtol, ctypes.c_void_p(self.scal.data_ptr()),
-                                         self._s()), "ode_init_norms")
-        v = self.scal[:2].cpu().numpy()
+        v = self._norms(self.y, self.K[0], None, self.n)
         return v[0], v[1]
 
     def rhs_euler(self, t, h):
         self._rhs(t, [self.K[0]], [1.0], h, self.f1)
 
     def diff_norm(self):
-        check(self.lib.gp_ode_init_norms(ctypes.c_void_p(self.y.data_ptr()), ctypes.c_void_p(self.K[0].data_ptr()),
-                                         ctypes.c_void_p(self.f1.data_ptr()), self.n, self.atol, self.rtol,
-                                         ctypes.c_void_p(self.scal.data_ptr()), self._s()), "ode_init_norms")
-        return self.scal[2:3].cpu().numpy()[0]
+        return self._norms(self.y, self.K[0], self.f1, self.n)
 
     def attempt(self, t, h):
         stage_t = [t + c * h for c in C[1:]] + [t + h]   # rk_step: fun(t + c * h, ...) for s = 1..5, then t + h
-        t32, sig, coef = self._device_stage_scalars(stage_t) if self.energy_grad else stage_scalars(stage_t)
+        en = self._entry("attempt")
+        t32, sig, coef = en.scalars(stage_t)
         self.y_new = torch.empty(self.n, dtype=torch.float64, device=self.dev)
-        fn, head = self._entry("gp_ode_attempt")
-        check(fn(
-            *head, ctypes.c_void_p(self.pobj.data_ptr()), t32.ctypes.data_as(ctypes.c_void_p),
+        check(en.fn(
+            *en.head, ctypes.c_void_p(self.pobj.data_ptr()), t32.ctypes.data_as(ctypes.c_void_p),
             sig.ctypes.data_as(ctypes.c_void_p), coef.ctypes.data_as(ctypes.c_void_p),
-            ctypes.c_void_p(self.y.data_ptr()), _ptr_array(self.K), _A6.ctypes.data_as(ctypes.c_void_p),
+            ctypes.c_void_p(self.y.data_ptr()), *en.extra, _ptr_array(self.K), _A6.ctypes.data_as(ctypes.c_void_p),
             _B6.ctypes.data_as(ctypes.c_void_p), _E7.ctypes.data_as(ctypes.c_void_p), float(h), self.rtol,
             self.atol, self.R, self.k, ctypes.c_void_p(self.y_new.data_ptr()),
             ctypes.c_void_p(self.scal[3:].data_ptr()), ctypes.c_void_p(self.ws.data_ptr()), self.ws.numel(),
-            self._s()), "ode_attempt")
+            self._s()), en.what)
         return self.scal[3:4].cpu().numpy()[0]
 
     def accept(self, t_old, t):
@@ -417,10 +444,7 @@ class DeviceRk45:
             if not (lo <= last < hi):
                 return
             i0, i1, base, rev = last, last + 1, last, 0
-        check(self.lib.gp_ode_dense(_ptr_array(self.K), _P74.ctypes.data_as(ctypes.c_void_p),
-                                    ctypes.c_void_p(self.y.data_ptr()), ctypes.c_void_p(self.t_eval_dev.data_ptr()),
-                                    i0, i1, base, rev, float(t_old), float(h), self.n,
-                                    ctypes.c_void_p(self.dense_out.data_ptr()), self._s()), "ode_dense")
+        _dense(self.lib, self.K, self.y, self.t_eval_dev, i0, i1, base, rev, t_old, h, self.dense_out, self._s())
 
     def outputs(self) -> torch.Tensor:
         """(n_t, R*9) fp64 outputs in solve_ivp order (all kept, or only the last). After a failed
@@ -443,40 +467,14 @@ class LikelihoodRk45(DeviceRk45):
         dev = heads.device
         y0 = torch.zeros(R * (arch.POSE_DIM + 1), dtype=torch.float64, device=dev)
         y0[: R * arch.POSE_DIM] = x0.reshape(-1).to(dev, torch.float64)
-        super().__init__(heads, pobj, y0, k, rtol, atol)
-        self.R = R
-        self.n = R * (arch.POSE_DIM + 1)
         if tuple(eps.shape) != (R, arch.POSE_DIM):
             raise ValueError(f"epsilon must be ({R}, {arch.POSE_DIM}), got {tuple(eps.shape)}")
+        super().__init__(heads, pobj, y0, k, rtol, atol, entries=arch.POSE_DIM + 1)
         self.eps = eps.to(dev, torch.float32).contiguous()
-        self.y = y0
-        self.K = [torch.empty(self.n, dtype=torch.float64, device=dev) for _ in range(N_STAGES + 1)]
-        self.f1 = torch.empty(self.n, dtype=torch.float64, device=dev)
-        self.ws = torch.empty(int(self.lib.gp_like_workspace_size(R)), dtype=torch.uint8, device=dev)
 
-    def _rhs(self, t, kin, acoef, h, kout):
-        t32, sig, coef = time_scalars(t)
-        nk = len(kin)
-        karr = _ptr_array(kin) if nk else None
-        aarr = (ctypes.c_double * nk)(*acoef) if nk else None
-        check(self.lib.gp_like_rhs(ctypes.byref(self.h.w), ctypes.c_void_p(self.pobj.data_ptr()), t32, sig, coef,
-                                   ctypes.c_void_p(self.y.data_ptr()), ctypes.c_void_p(self.eps.data_ptr()), karr,
-                                   aarr, nk, float(h), self.R, self.k, ctypes.c_void_p(kout.data_ptr()),
-                                   ctypes.c_void_p(self.ws.data_ptr()), self.ws.numel(), self._s()), "like_rhs")
-
-    def attempt(self, t, h):
-        stage_t = [t + c * h for c in C[1:]] + [t + h]
-        t32, sig, coef = stage_scalars(stage_t)
-        self.y_new = torch.empty(self.n, dtype=torch.float64, device=self.dev)
-        check(self.lib.gp_like_attempt(
-            ctypes.byref(self.h.w), ctypes.c_void_p(self.pobj.data_ptr()), t32.ctypes.data_as(ctypes.c_void_p),
-            sig.ctypes.data_as(ctypes.c_void_p), coef.ctypes.data_as(ctypes.c_void_p),
-            ctypes.c_void_p(self.y.data_ptr()), ctypes.c_void_p(self.eps.data_ptr()), _ptr_array(self.K),
-            _A6.ctypes.data_as(ctypes.c_void_p), _B6.ctypes.data_as(ctypes.c_void_p),
-            _E7.ctypes.data_as(ctypes.c_void_p), float(h), self.rtol, self.atol, self.R, self.k,
-            ctypes.c_void_p(self.y_new.data_ptr()), ctypes.c_void_p(self.scal[3:].data_ptr()),
-            ctypes.c_void_p(self.ws.data_ptr()), self.ws.numel(), self._s()), "like_attempt")
-        return self.scal[3:4].cpu().numpy()[0]
+    def _entry(self, name: str) -> _Entry:
+        return _Entry(getattr(self.lib, "gp_like_" + name), (ctypes.byref(self.h.w),),
+                      (ctypes.c_void_p(self.eps.data_ptr()),), stage_scalars, "like_" + name)
 
     def set_t_eval(self, t_eval, direction, keep_all):
         raise NotImplementedError("the likelihood solve has no t_eval (samplers.py:97-99)")
@@ -506,21 +504,15 @@ class GlobalDeviceRk45(DeviceRk45):
         raise NotImplementedError("global-batch RK45 keeps only the final output (rk45_device)")
 
     def init_norms(self):
+        """Over the whole batch's y and f0, gathered here and kept for diff_norm."""
         self._y_full, self._f0_full = self._full(self.y), self._full(self.K[0])
-        check(self.lib.gp_ode_init_norms(ctypes.c_void_p(self._y_full.data_ptr()),
-                                         ctypes.c_void_p(self._f0_full.data_ptr()), None, self.n_total, self.atol,
-                                         self.rtol, ctypes.c_void_p(self.scal.data_ptr()), self._s()), "ode_init_norms")
-        v = self.scal[:2].cpu().numpy()
+        v = self._norms(self._y_full, self._f0_full, None, self.n_total)
         return v[0], v[1]
 
     def diff_norm(self):
-        f1 = self._full(self.f1)
-        check(self.lib.gp_ode_init_norms(ctypes.c_void_p(self._y_full.data_ptr()),
-                                         ctypes.c_void_p(self._f0_full.data_ptr()), ctypes.c_void_p(f1.data_ptr()),
-                                         self.n_total, self.atol, self.rtol, ctypes.c_void_p(self.scal.data_ptr()),
-                                         self._s()), "ode_init_norms")
+        d = self._norms(self._y_full, self._f0_full, self._full(self.f1), self.n_total)
         self._y_full = self._f0_full = None
-        return self.scal[2:3].cpu().numpy()[0]
+        return d
 
     def attempt(self, t, h):
         raise NotImplementedError("global-batch RK45 runs the device controller (rk45_device)")
@@ -780,9 +772,7 @@ def rk45_device(be: DeviceRk45, t0: float, t_bound: float, t_eval: Optional[np.n
         step_k[0], step_k[N_STAGES] = step_k[N_STAGES], step_k[0]     # undo the FSAL swap
         tev = torch.tensor([t_eval[-1]], dtype=torch.float64, device=dev)
         out = torch.empty((1, be.n), dtype=torch.float64, device=dev)
-        check(lib.gp_ode_dense(_ptr_array(step_k), _P74.ctypes.data_as(ctypes.c_void_p),
-                               ctypes.c_void_p(ybuf[ctl.yi ^ 1].data_ptr()), ctypes.c_void_p(tev.data_ptr()), 0, 1, 0,
-                               0, float(ctl.t_old), float(ctl.t - ctl.t_old), be.n, ctypes.c_void_p(out.data_ptr()),
-                               ctypes.c_void_p(stream.cuda_stream)), "ode_dense")
+        _dense(lib, step_k, ybuf[ctl.yi ^ 1], tev, 0, 1, 0, 0, ctl.t_old, ctl.t - ctl.t_old, out,
+               ctypes.c_void_p(stream.cuda_stream))
         x = out[0]
     return x, int(ctl.nfev), int(ctl.status)

@@ -292,3 +292,54 @@ def test_c_host_pc_sample_global_one_shard_and_exchange_failure():
         assert "exchange" in lib.gp_last_error().decode()
     finally:
         lib.gp_weights_free(h)
+
+
+@pytest.fixture(scope="module")
+def ode_entry_args():
+    """Valid small arguments of the six raw ODE entries (R = 16 rows, one object of k = 16), filled outputs."""
+    from genpose2_amd import _lib, ode
+    from genpose2_amd.agent import PoseNet
+    from genpose2_amd.config import GenPoseConfig
+    R, K, fill = 16, 16, 7.25
+    heads = PoseNet(GenPoseConfig(device=DEV, sampler_mode=["ode"])).eval().heads
+    gen = torch.Generator(DEV).manual_seed(11)
+    f64 = dict(dtype=torch.float64, device=DEV)
+    a = dict(lib=_lib.load(), R=R, K=K, fill=fill, heads=heads,
+             pobj=torch.randn(1, 768, device=DEV, generator=gen),
+             y=torch.randn(R * 10, generator=gen, **f64), eps=torch.randn(R, 9, device=DEV, generator=gen),
+             k=[torch.full((R * 10,), fill, **f64) for _ in range(7)], y1=torch.full((R * 10,), fill, **f64),
+             err=torch.full((1,), fill, **f64), ws=torch.zeros(int(_lib.load().gp_ode_workspace_size(R)),
+                                                              dtype=torch.uint8, device=DEV))
+    a["scal"] = ode.stage_scalars([0.5 - 0.01 * c for c in (0.2, 0.3, 0.8, 8 / 9, 1.0, 1.0)])
+    return a
+
+
+@pytest.mark.parametrize("name", ["ode_rhs", "like_rhs", "ode_rhs_energy", "ode_attempt", "like_attempt",
+                                  "ode_attempt_energy"])
+def test_ode_entries_refuse_an_empty_workspace(ode_entry_args, name):
+    """Each raw right-hand side and host-controlled attempt, called with valid buffers and workspace_bytes = 0,
+    returns a status before any launch; the message carries the entry's own name and "workspace too small"."""
+    from genpose2_amd import ode
+    a = ode_entry_args
+    lib, h, R, K = a["lib"], a["heads"], a["R"], a["K"]
+    t32, sig, coef = a["scal"]
+    s = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    np_p = lambda v: v.ctypes.data_as(ctypes.c_void_p)   # noqa: E731
+    head = (ctypes.byref(h.w), ctypes.byref(h.grad_weights)) if name.endswith("_energy") else (ctypes.byref(h.w),)
+    extra = (_vp(a["eps"]),) if name.startswith("like_") else ()
+    kptr = (ctypes.c_void_p * 7)(*[t.data_ptr() for t in a["k"]])
+    if "_rhs" in name:
+        rc = getattr(lib, "gp_" + name)(*head, _vp(a["pobj"]), float(t32[0]), float(sig[0]), float(coef[0]),
+                                        _vp(a["y"]), *extra, None, None, 0, 0.0, R, K, _vp(a["k"][1]), _vp(a["ws"]),
+                                        0, s)
+    else:
+        rc = getattr(lib, "gp_" + name)(*head, _vp(a["pobj"]), np_p(t32), np_p(sig), np_p(coef), _vp(a["y"]), *extra,
+                                        kptr, np_p(ode._A6), np_p(ode._B6), np_p(ode._E7), -0.01, 1e-5, 1e-5, R, K,
+                                        _vp(a["y1"]), _vp(a["err"]), _vp(a["ws"]), 0, s)
+    msg = lib.gp_last_error().decode()
+    assert rc != 0, name
+    assert name + ":" in msg and "workspace too small" in msg, (name, msg)
+    torch.cuda.synchronize()
+    for t in a["k"] + [a["y1"], a["err"]]:
+        assert bool((t == a["fill"]).all())
+    assert not bool(a["ws"].any())
